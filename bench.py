@@ -12,14 +12,19 @@ collective in the timed region.  By default every rank's share is the
 headline's 65536 x 64 KiB (weak scaling: the global batch is N x 4 GiB), so
 the 1/2/4/8 series is one per-GPU workload; --config c5 splits C5's fixed
 2^20 x 64 KiB batch instead (strong).  After timing: RCCL all_gather of the
-per-share CRC arrays (global payload order) and of the timings.  Under
-torchrun the process group is formed at every world size, 1 included.
+timings.  Under torchrun the process group is formed at every world size,
+1 included.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` (HIP-event kernel time vs HBM peak; `traffic` from the committed
-PMC profile, scaled to rank 0's share at N > 1) and `cpu_baseline` (the
-oracle timed on this host's cores, at every N, on rank 0 after timing) --
-the oracle also checks the gathered CRCs of every share (`parity`).
+A plain run sets up, warms up, times the steps and prints ONE JSON line on
+rank 0, with `roofline` (HIP-event kernel time of the same timed steps vs HBM
+peak; `traffic` from the committed PMC profile, scaled to rank 0's share at
+N > 1).  --dump-outputs DIR also writes what the last timed step returned
+(dump_outputs).  Everything else runs only with --full: the RCCL all_gather
+of the per-share CRC arrays (global payload order), `cpu_baseline` (the
+oracle timed on this host's cores, at every N, on rank 0 after timing) -- the
+oracle also checks the gathered CRCs of every share (`parity`) -- and, for
+the headline, the `e2e` and `c5_strong` sub-records; for c2 the cache-warm
+replay (`rotation`); for msgs the flipped-bit check (`verify`).
 """
 from __future__ import annotations
 
@@ -82,6 +87,15 @@ def parse():
     p.add_argument("--streams", type=int, default=1,
                    help="issue consecutive steps round-robin on this many streams (independent batches, "
                         "fixed and offsets layouts)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps also run everything else this benchmark measures or checks: "
+                        "the CPU baseline and the oracle parity check, the e2e and c5_strong sub-records of the "
+                        "headline, c2's cache-warm replay, msgs' flipped-bit check (a plain run only sets up, warms "
+                        "up, times the steps and prints the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to DIR/<name>.npy (float64, "
+                        "exact; see dump_outputs); the inputs depend only on the arguments, so two builds can be "
+                        "compared output for output")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=1.5, help="wall budget of the CPU baseline sample")
     p.add_argument("--parity-samples", type=int, default=64)
@@ -129,6 +143,8 @@ def main():
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={env_world}")
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.config is None:
         # every N runs the headline's per-GPU batch (65536 x 64 KiB per rank,
         # weak scaling), so the driver's 1/2/4/8 series is one workload
@@ -196,18 +212,18 @@ def main():
     if args.backend == "nccl" and len(set(keys)) != world:
         sys.exit(f"bench.py: ranks share a GPU ({pcis}): one GPU per rank")
 
-    # The sub-records run before the headline, so the headline's dispatches
+    # The sub-records (--full only) run before the headline, so the headline's dispatches
     # are the last of their kernel in a profile of this command, in the order
     # e2e, c5_strong, headline: with the PCIe-bound e2e second between
     # c5_strong and the headline, the headline measured ~1% lower and noisier
     # (0.837-0.856 vs 0.854-0.857 on one box, profiles/r06/order/).
     e2e = None
-    if args.config == "metric" and not args.no_e2e and world == 1:
+    if args.full and args.config == "metric" and not args.no_e2e and world == 1:
         # north_star's end-to-end rate: the headline's bytes starting and
         # ending in host memory (NA recv buffers / hg_proc buffers)
         e2e = run_e2e(args, torch, dev)
     c5_strong = None
-    if args.config == "metric" and not args.no_c5_strong:
+    if args.full and args.config == "metric" and not args.no_c5_strong:
         # BASELINE configs[4] in the same run, whatever flags the driver
         # passes: C5's fixed 2^20 x 64 KiB batch split over the ranks (strong
         # scaling)
@@ -359,9 +375,17 @@ def main():
         dist.barrier()
     wall = time.perf_counter() - t0
     kern_ms = ev_start.elapsed_time(ev_end) / args.steps
+    dump = None
+    if args.dump_outputs:
+        # what the last timed step returned to its caller, copied before any
+        # later launch can write the same buffers
+        if layout == "messages":
+            dump = {"status": status.clone(), "mismatches": mism.clone()}
+        else:
+            dump = {"crcs": outs[(args.steps - 1) % len(streams)].clone()}
 
     rotation = None
-    if rotate > 1:
+    if rotate > 1 and args.full:
         # every copy gives the same CRCs, and the replay figure of copy 0 alone
         # (each launch re-reads what the last one left in the Infinity Cache),
         # kept only as a labelled cache-warm number
@@ -395,7 +419,7 @@ def main():
     # ---- gathered result (outside the timed region) ----------------------
     crcs = out
     verify_note = None
-    if layout == "messages":
+    if layout == "messages" and args.full:
         # every timed verify passed (the mismatch counter accumulates over all
         # launches), and one flipped payload bit is caught exactly where it is
         bad_before = int(mism.item())
@@ -407,17 +431,25 @@ def main():
         data[pos] ^= 0x10
         verify_note = (f"{args.steps + args.warmup + 1} verify launches: {bad_before} mismatches; one flipped bit "
                        f"flagged {flagged} (expected [{victim}])")
+    if layout == "messages":
         crcs = sender  # the sender-side CRCs, checked against the oracle below
-    if dist_on:
-        # RCCL all_gather of the per-rank CRC arrays (padded to the largest
-        # shard: ranks may hold different counts), then trimmed in rank order:
-        # the global batch's CRCs in global payload order (messages: the
-        # sender's interleaved header/payload pieces, two per message)
-        counts = plan.counts if plan is not None else [count] * world
-        if layout == "messages":
-            counts = [2 * c for c in counts]
-        crcs = gather_shares(dist, crcs, counts, world, coll_dev)
-    got = G.as_unsigned(crcs) if rank == 0 else None
+    share_counts = plan.counts if plan is not None else [count] * world
+    got = None
+    if args.full:
+        if dist_on:
+            # RCCL all_gather of the per-rank CRC arrays (padded to the largest
+            # shard: ranks may hold different counts), then trimmed in rank order:
+            # the global batch's CRCs in global payload order (messages: the
+            # sender's interleaved header/payload pieces, two per message)
+            counts = [2 * c for c in share_counts] if layout == "messages" else share_counts
+            crcs = gather_shares(dist, crcs, counts, world, coll_dev)
+        got = G.as_unsigned(crcs) if rank == 0 else None
+    if dump is not None:
+        if dist_on:  # every rank's arrays, in rank (= global payload) order
+            dump = {k: gather_shares(dist, v, [1] * world if k == "mismatches" else share_counts, world, coll_dev)
+                    for k, v in dump.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in dump.items()})
 
     bytes_all = torch.tensor([float(payload_bytes)], dtype=torch.float64, device=coll_dev)
     if dist_on:
@@ -449,6 +481,7 @@ def main():
             result["c5_strong"] = c5_strong
         if rotation is not None:
             result["rotation"] = rotation
+        if rotate > 1:
             result["roofline"]["cache"] = (f"cold: step i reads copy i % {rotate} of {rotate} at distinct addresses "
                                            f"({rotate * payload_bytes / 2**20:.0f} MiB in all)")
         if e2e is not None:
@@ -462,8 +495,9 @@ def main():
 
 def report(args, r):
     """Rank 0's JSON line of one run (r: the run's shape, shares, timings and
-    gathered CRCs, assembled by main).  The oracle runs here, after timing, at
-    every N: the CPU baseline, and the parity check of every rank's share."""
+    gathered CRCs, assembled by main).  With --full the oracle runs here, after
+    timing, at every N: the CPU baseline, and the parity check of every rank's
+    share."""
     traffic, traffic_src = pmc_traffic(r.config, r.world, r.alg_bytes)
     metric = {"metric": "GiB/s checksummed (device-resident), CRC32c, 64K x 64 KiB payloads",
               "c5": "GiB/s checksummed (device-resident), CRC32c, 1M x 64 KiB payloads split over the GPUs (C5)"}
@@ -502,7 +536,9 @@ def report(args, r):
                      "frac": round(r.achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                      "kernel_ms": round(r.kern_ms_max, 4), "algorithmic_bytes_per_launch": r.alg_bytes},
     }
-    if not args.no_cpu_baseline:
+    if not getattr(args, "full", True):  # (a direct caller that does not say gets the oracle legs)
+        result["parity"] = "unchecked (plain run; --full checks the CRCs against the oracle)"
+    elif not args.no_cpu_baseline:
         # the only leg that runs the oracle: timed on a bounded sample on this
         # host's cores, and the checker of the gathered CRCs -- that sample,
         # the first and last payload of every rank's share and random payloads
@@ -522,6 +558,31 @@ def report(args, r):
     if r.verify_note:
         result["verify"] = r.verify_note
     return result
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write `arrays` (name -> integer numpy array) as
+    DIR/<name>.npy in float64, every value exact: 64-bit CRCs as two arrays of
+    32-bit halves, <name>_hi and <name>_lo.  At most DUMP_LIMIT_BYTES in all:
+    a larger output is cut to a fixed, seeded sample of its elements (the
+    same positions in every run)."""
+    files = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype.itemsize == 8:
+            u = a.view(np.uint64)
+            files[name + "_hi"], files[name + "_lo"] = u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)
+        else:
+            files[name] = a.view(np.dtype(f"u{a.dtype.itemsize}"))  # CRC-32s are stored in signed words
+    budget = (DUMP_LIMIT_BYTES // len(files) - 256) // 8  # elements per file (256: room for the .npy header)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in files.items():
+        if a.size > budget:
+            a = a[np.sort(np.random.default_rng(0xD0).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
 
 
 def pci_address(torch, dev):
@@ -821,21 +882,14 @@ def bench_c1(args):
     if not os.path.exists(exe):
         subprocess.run(["make", "-s", "-C", ROOT, "build/c1_bench"], check=True)
     host = O.splitmix_bytes(count * length, seed)
-    steps = max(args.steps, 200)
+    steps = args.steps
     r = subprocess.run([exe, str(count), str(length), str(steps), str(args.warmup)], input=host.tobytes(),
                        capture_output=True, check=True)
     el, first, xsum = r.stdout.decode().split()
     el = float(el)
-    want = [O.crc(method, struct.pack("<I", length) + host[i * length:(i + 1) * length].tobytes())
-            for i in range(count)]
-    wx = 0
-    for w in want:
-        wx ^= w
-    ok = int(first) == want[0] and int(xsum) == wx
-    ref_t0 = time.perf_counter()
-    for _ in range(steps):
-        O.batch_fixed(method, host, length, length, count, variant="sse42", nthreads=1)
-    ref_el = time.perf_counter() - ref_t0
+    if args.dump_outputs:  # what the driver returns: the first payload's CRC and the xor of all of them
+        dump_outputs(args.dump_outputs, {"first_crc": np.array([int(first)], dtype=np.uint64),
+                                         "xor_of_crcs": np.array([int(xsum)], dtype=np.uint64)})
     res = {"metric": "GiB/s checksummed on the host CPU through the mchecksum API, c1",
            "value": round(count * (length + 4) * steps / el / 2**30, 3), "unit": "GiB/s", "n_gpus": 0,
            "steps": steps, "warmup": args.warmup, "ms_per_step": round(el / steps * 1e3, 4),
@@ -843,10 +897,22 @@ def bench_c1(args):
            "data": "synthetic (splitmix64 bytes)",
            "config": {"workload": "crc32c, 1024 x (4 B length field + 4 KiB raw bytes) via reset/update/update/get",
                       "threads": 1, "driver": "tools/c1_bench.c"},
-           "parity": "bit-exact (all 1024 payloads: first + xor-sum vs oracle)" if ok else "MISMATCH",
-           "cpu_baseline": {"value": round(count * length * steps / ref_el / 2**30, 3), "unit": "GiB/s",
-                            "cores": 1, "kind": "port", "variant": "x86 SSE4.2 crc32 instruction (oracle)",
-                            "sample": f"{steps} passes over the same 1024 x 4 KiB buffers"}}
+           "parity": "unchecked (plain run; --full checks the CRCs against the oracle)"}
+    if args.full:
+        want = [O.crc(method, struct.pack("<I", length) + host[i * length:(i + 1) * length].tobytes())
+                for i in range(count)]
+        wx = 0
+        for w in want:
+            wx ^= w
+        ok = int(first) == want[0] and int(xsum) == wx
+        ref_t0 = time.perf_counter()
+        for _ in range(steps):
+            O.batch_fixed(method, host, length, length, count, variant="sse42", nthreads=1)
+        ref_el = time.perf_counter() - ref_t0
+        res["parity"] = "bit-exact (all 1024 payloads: first + xor-sum vs oracle)" if ok else "MISMATCH"
+        res["cpu_baseline"] = {"value": round(count * length * steps / ref_el / 2**30, 3), "unit": "GiB/s",
+                               "cores": 1, "kind": "port", "variant": "x86 SSE4.2 crc32 instruction (oracle)",
+                               "sample": f"{steps} passes over the same 1024 x 4 KiB buffers"}
     print(json.dumps(res), flush=True)
     return res
 

@@ -1,6 +1,6 @@
 """bench.py's RCCL leg on the one-GPU box.
 
-`torchrun --nproc-per-node 1 bench.py --gpus 1` forms the process group with
+`torchrun --nproc-per-node 1 bench.py --gpus 1 --full` forms the process group with
 the nccl (= RCCL) backend even at world size 1 (bench.py: the group exists
 whenever WORLD_SIZE is set), so the calls the driver's 8-GPU run makes --
 init_process_group("nccl", device_id=...), the device all_gather of the
@@ -37,7 +37,7 @@ def _torchrun(config, extra=()):
     torch.cuda.empty_cache()  # the child allocates its own batch (C5: 64 GiB)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--config", config, "--steps", "3", "--warmup", "2", "--cpu-seconds", "0.3",
+           "--gpus", "1", "--config", config, "--full", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0.3",
            "--parity-samples", "16", *extra]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)

@@ -9,12 +9,12 @@ step pytest
 timeout -k 10 700 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=$?; tail -4 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 for c in ${CONFIGS:-metric c2 c3 c4 seg}; do
   step "bench $c"
-  timeout -k 10 300 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --config $c --full > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
   cat $O/bench_$c.json
 done
 for c in metric c4; do
   step "torchrun 2 ranks $c (gloo rehearsal on one GPU)"
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --config $c --gpus 2 --backend gloo --steps 5 --warmup 2 > $O/bench_2rank_gloo_$c.json 2> $O/bench_2rank_gloo_$c.err || { tail -20 $O/bench_2rank_gloo_$c.err; exit 1; }
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --config $c --gpus 2 --backend gloo --full --steps 5 --warmup 2 > $O/bench_2rank_gloo_$c.json 2> $O/bench_2rank_gloo_$c.err || { tail -20 $O/bench_2rank_gloo_$c.err; exit 1; }
   cat $O/bench_2rank_gloo_$c.json
 done
 cd /tmp && export TMPDIR=/tmp
