@@ -143,7 +143,10 @@ mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf,
  * outside [first[0], first[nobj]) are ignored.  dev_work: caller-owned device
  * scratch (8-byte aligned) of at least mchecksum_gpu_segments_work_size(nseg)
  * bytes, not shared with a concurrent call (SIZE_MAX for nseg > 2^40, which
- * is rejected).  Every 32/64-bit method.  Segments are
+ * is rejected).  A call captured into a graph may be replayed after the
+ * contents of dev_seg_addr, dev_seg_len and dev_obj_first have changed (every
+ * replay scans the tables again), one replay at a time per workspace.
+ * Every 32/64-bit method.  Segments are
  * cut into 256 KiB chunks hashed in parallel and recombined with GF(2) shift
  * operators, so one huge segment still spreads over the whole GPU. */
 MCHECKSUM_PUBLIC size_t

@@ -95,8 +95,21 @@ struct SegArgs {
 // its offset by a decoupled look-back over the blocks before it: one wave
 // reads 64 predecessors' descriptors at once and sums aggregates back to the
 // nearest published inclusive prefix, then publishes its own inclusive prefix.
-// Descriptors carry the call's epoch (a process-wide counter from a random
-// seed), so a workspace left by an earlier call needs no clearing.  The wait
+// Descriptors carry the call's tag: its key -- scan_key(epoch, gen), the epoch
+// a process-wide counter from a random seed, gen the workspace's count of
+// scans -- above the 2 state bits.  A workspace left by an earlier call needs
+// no clearing, and neither does one left by an earlier replay of the same
+// captured call: a graph replays the epoch it captured, so the epoch alone
+// would let block b take block b - 1's inclusive prefix of the LAST replay
+// (state 2, same epoch) for this one's whenever b looks back before b - 1 has
+// published -- right only while the lengths never change.  gen differs: every
+// block reads it before its first flag store (the release orders the read
+// first), and the last block bumps it only after its look-back, which ends at
+// an inclusive prefix carrying this call's tag and so, by induction down to
+// block 0, after every block of the call has published -- hence read gen.
+// All blocks of a call therefore read the same gen, calls on one workspace
+// are serialized (header), so each call's gen is its predecessor's + 1, and
+// two tags of one epoch are equal only 2^62 scans apart.  The wait
 // depends only on blocks dispatched before this one (a kernel's workgroups
 // are dispatched in order and run to completion), and is bounded: a give-up
 // is counted as a queue fault and reported on the caller's error word.
@@ -189,8 +202,9 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 
 // Wave 0 of block b: publish (tp, tc, tr), look back, publish the inclusive
 // prefix; returns the exclusive prefix (bytes, chunks, ragged) in every lane.
-// false: the bounded wait gave up (fault counted).
-__device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_t epoch, uint64_t tp, uint64_t tc,
+// tag: the call's key above the two state bits (scan_block).  false: the
+// bounded wait gave up (fault counted).
+__device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_t tag, uint64_t tp, uint64_t tc,
                                              uint64_t tr, uint32_t lane, uint64_t *ep, uint64_t *ec, uint64_t *er,
                                              uint64_t fault_block) {
     uint64_t *me = desc + kDescWords * b;
@@ -210,7 +224,7 @@ __device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_
             st_relaxed(me + 5, tc);
             st_relaxed(me + 6, tr);
         }
-        __hip_atomic_store(me, epoch * 4 + (b == 0 ? 2u : 1u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(me, tag | (b == 0 ? 2u : 1u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     uint64_t sp = 0, sc = 0, sr = 0;
     bool ok = true;
@@ -228,8 +242,9 @@ __device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_
             (void)fault_block;
 #endif
             const int64_t idx = k - (int64_t)lane;
-            const uint64_t f = idx >= 0 ? ld_relaxed(desc + kDescWords * (uint64_t)idx) : epoch * 4 + 2;
-            const uint32_t state = (f >> 2) == epoch ? (uint32_t)(f & 3u) : 0u;
+            // (the lanes past block 0 present this call's own tag: an inclusive prefix of 0)
+            const uint64_t f = idx >= 0 ? ld_relaxed(desc + kDescWords * (uint64_t)idx) : tag | 2u;
+            const uint32_t state = (f & ~3ull) == tag ? (uint32_t)(f & 3u) : 0u;
             const unsigned long long incl = __ballot(state == 2), none = __ballot(state == 0);
             const uint32_t S = incl ? (uint32_t)__builtin_ctzll(incl) : 64u;  // nearest inclusive prefix
             const unsigned long long below = S >= 64 ? ~0ull : ((1ull << S) - 1);
@@ -260,7 +275,7 @@ __device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_
             st_relaxed(me + 4, sp + tp);
             st_relaxed(me + 5, sc + tc);
             st_relaxed(me + 6, sr | tr);
-            __hip_atomic_store(me, epoch * 4 + 2, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(me, tag | 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     *ep = sp;
@@ -368,10 +383,12 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
     if (w == 0) {
         // the workspace's call count, read before this block publishes: the
         // last block bumps it only after its look-back saw every block's
-        // descriptor, so all blocks of the call read the same count
+        // descriptor, so all blocks of the call read the same count -- and
+        // tag their descriptors with it: the key's low 62 bits above the state
         const uint64_t gen = uniform(ld_relaxed(sa.gen));
         uint64_t ep, ec, er;
-        const bool ok = seg_lookback(sa.desc, b, sa.epoch, tp, tc, *rag, lane, &ep, &ec, &er, sa.fault_block);
+        const bool ok = seg_lookback(sa.desc, b, scan_key(sa.epoch, gen) << 2, tp, tc, *rag, lane, &ep, &ec, &er,
+                                     sa.fault_block);
         if (lane == 0) {
             ex[0] = ep;
             ex[1] = ec;
@@ -490,6 +507,10 @@ struct ChunkWalk {
             *end = a->P[a->first[j + 1]];
             *stop = a->P[s] + off + *n;
             *head = a->P[s] + off == a->P[a->first[j]];
+            // an untrusted scan again: prefixes that put the chunk past its
+            // object's end would shift by a wrapped count (shift32 indexes
+            // its operators by that count's hex digits, 12 of them held)
+            if (*stop > *end) *in = false;
         }
         c++;
         return true;
@@ -657,6 +678,12 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         if (have) locate(c, &cur);
         if (have && cur.even) issue(ring, cur);
         while (have) {
+            // an untrusted scan (seg_locate): prefixes that put the chunk past
+            // its object's end would shift by a wrapped count (shift64 indexes
+            // its operators by that count's hex digits, 12 of them held) --
+            // skipped as the others.  Tested here, not in locate(): the next
+            // chunk's first loads do not wait for its object's end offset.
+            if (cur.in && cur.stop > cur.end) cur.in = cur.even = false;
             const uint8_t *q = reinterpret_cast<const uint8_t *>(cur.p);
             // the object's first chunk starts from the register init (in its
             // first 8 bytes; Z^n(init) for a shorter, ragged chunk)

@@ -271,11 +271,34 @@ class SegmentBatch:
         self.nobj = len(first) - 1
         self.device = dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
         self.bytes = int(np.sum(np.asarray(lens, dtype=np.int64)[first[0]:first[-1]])) if self.nseg else 0
+        self._cap = np.asarray(lens, dtype=np.int64)  # each segment's size as given: set_lengths stays within it
+        self._span = (int(first[0]), int(first[-1]))
         self.meta = torch.from_numpy(np.concatenate([np.asarray(addr, dtype=np.uint64).view(np.int64),
                                                      np.asarray(lens, dtype=np.int64), first])).to(self.device)
         self.work = torch.empty((_lib().mchecksum_gpu_segments_work_size(self.nseg) + 7) // 8, dtype=torch.int64,
                                 device=self.device)
         self._last = None  # (stream handle, its torch stream, event after the call or None) of the last call
+
+    def set_lengths(self, lens, stream=None) -> None:
+        """Overwrite the device length table in place: segment s now covers the
+        first lens[s] bytes of the tensor it was built from.  For a captured
+        `checksum` (every replay scans the table again) and for tests: the
+        copy is enqueued on `stream` (default: the current one) and nothing
+        else happens per call -- order it before the replay that should see
+        it and after the one before.  Not while that stream is capturing."""
+        import numpy as np
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        if lens.ndim != 1 or len(lens) != self.nseg:
+            raise GpuChecksumError(f"set_lengths needs {self.nseg} lengths")
+        if np.any(lens < 0) or np.any(lens > self._cap):
+            raise GpuChecksumError("a length is negative or larger than its segment")
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            stream = torch.cuda.ExternalStream(int(stream), device=self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):  # (None: the current stream stays)
+            if torch.cuda.is_current_stream_capturing():
+                raise GpuChecksumError("set_lengths during graph capture: the copy would bake these lengths in")
+            self.meta[self.nseg:2 * self.nseg].copy_(torch.from_numpy(lens))
+        self.bytes = int(np.sum(lens[self._span[0]:self._span[1]])) if self.nseg else 0
 
     def checksum(self, method: str, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if out is None:
