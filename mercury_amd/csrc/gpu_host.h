@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "crc_gpu_device.h"
+#include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
 
 namespace mck {
@@ -114,18 +115,25 @@ extern std::mutex g_mu;  // creation of contexts and tables only
 // Record a formatted error for mchecksum_gpu_last_error(); returns rc.
 int set_err(int rc, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_err(hipError_t e, const char *what);
-// Method -> model index for GPU batch kernels (32/64-bit): -1 unknown, -2 no kernel.
-int gpu_model(const char *method, int *width);
-// The kernels' form of catalogue model idx (MSB-first models in the byte-
-// reversed register domain, crc_gpu_layout.h), and whether it is MSB-first:
-// then the host byte-swaps the outputs after the launch (swap_outputs).
+// A method name resolved once per call: the catalogue index, the width and
+// whether the model is MSB-first -- then the kernels work in the byte-reversed
+// register domain (crc_gpu_layout.h) and the host byte-swaps the outputs after
+// the launch (swap_outputs).
+struct Model {
+    int idx = -1, width = 0;
+    bool msb = false;
+};
+// Method -> model for GPU batch kernels (32/64-bit): 0, -1 unknown, -2 no kernel.
+int gpu_model(const char *method, Model *out);
+// The same, with the error text recorded: MCHECKSUM_GPU_OK or _EMETHOD.
+int resolve_model(const char *method, Model *out);
+// The kernels' form of catalogue model idx.
 crc_rmodel_t gpu_rmodel(int idx);
-bool gpu_msb(int idx);
 int swap_outputs(void *dev_out, uint64_t count, int width, void *stream);
 // Current device's context, created on first use (takes g_mu then only).
 int device_ctx(DevCtx **out);
-// Model + device context + table pack for lanes-per-payload 2^log2g (g_mu on creation only).
-int prologue(const char *method, int log2g, int *width, DevCtx **c, const void **pack);
+// The device table pack of model idx for lanes-per-payload 2^log2g (g_mu on creation only).
+int get_pack(DevCtx *c, int idx, int log2g, const void **pack);
 // Per-device, per-model extension tables (mchecksum_gpu_ext.hip): the
 // Z^n shift pack of a 32/64-bit model, the byte table of a 16-bit one
 // (g_mu on creation only).
@@ -138,6 +146,20 @@ int get_ext(DevCtx *c, int idx, const void **out);
 SlotRef queue_slot(DevCtx *c, void *stream);
 void slot_issued(SlotRef &r);
 void slot_unissue(DevCtx *c, SlotRef &r);
+// Launch `kernel` with the slot r took from queue_slot (or none: an empty r):
+// its completion records r.done; a failed launch call is taken back from the
+// slot and reported as `what`.
+template <class A>
+int launch_slot(DevCtx *c, SlotRef &r, void (*kernel)(A), unsigned grid, int block, void *stream, const A &args,
+                const char *what) {
+    const hipError_t e = launch_kernel(kernel, dim3(grid), dim3(block), (hipStream_t)stream, r.done, args);
+    if (e != hipSuccess) {
+        slot_unissue(c, r);
+        return hip_err(e, what);
+    }
+    slot_issued(r);
+    return MCHECKSUM_GPU_OK;
+}
 // Queue-fault count of mchecksum_gpu_ext.hip's kernels (their own copy of
 // g_mck_queue_faults) on the current device; -1 on error.
 long long ext_queue_faults();

@@ -1,0 +1,224 @@
+// launch_plan.h -- which batch kernel a call launches, and how: a pure
+// function of the call's shape, the device's CU count and ONE settings
+// snapshot (the entry point reads mck_settings() once and passes it down, so
+// mchecksum_gpu_reload_settings() on another thread cannot change a launch
+// half way through its decisions).  No HIP runtime call, no global: the host
+// compiles and checks it on the CPU (tests/native/launch_plan.cpp); the
+// kernels themselves are looked up from a plan in mchecksum_gpu.hip
+// (kernel_for).
+#ifndef MCK_LAUNCH_PLAN_H
+#define MCK_LAUNCH_PLAN_H
+
+#include <cstddef>
+#include <cstdint>
+
+#include "crc_gpu_device.h"
+#include "mchecksum_models.h"
+
+namespace mck {
+
+// The work queue counts chunk ids and per-workgroup slots in 32 bits
+// (crc_gpu_device.h, WgQueue): 2^31 payloads per call keeps both in range.
+constexpr uint64_t kMaxUnits = 1ull << 31;
+
+struct LaunchPlan {
+    int width = 0;         // 32 or 64
+    int lg = 0;            // log2 lanes per payload (the table pack's), after the count / CU adjustment
+    int mode = 0;          // kFixedAligned / kFixedGeneric / kOffsets
+    bool light = false;    // small-batch CRC-32C layout
+    bool aligned = false;  // mode == kFixedAligned
+    bool nt = false;       // the kernel's non-temporal payload loads
+    bool split = false;    // CRC-64 payloads as kSplitBytes pieces on the work queue
+    uint32_t split_log2 = 0;    // log2 pieces per payload (split only)
+    bool split_lds_ok = false;  // split: pieces combine in their workgroup IF the launch gets a slot
+    bool zero_out = false;      // split: out[] is zeroed before the launch whether it gets a slot or not
+    bool dyn = false;      // takes a work-queue slot (dyn_policy, or split)
+    uint64_t units = 0;    // waves' worth of work: payload groups, payloads (offsets) or pieces (split)
+    int block = 0, blocks_per_cu = 0;
+    unsigned grid = 0;
+};
+
+// MCHECKSUM_GPU_LOG2G=g: 2^g lanes per payload for every fixed batch (A/B)
+inline bool lg_forced(const mck_settings_t &s) { return s.gpu_log2g >= 0; }
+// (the settings parser admits 0..CRC_GPU_MAX_LOG2G only; anything larger in a
+// hand-made snapshot reads as the largest, so lg always indexes a pack)
+inline int forced_lg(const mck_settings_t &s) { return s.gpu_log2g > CRC_GPU_MAX_LOG2G ? CRC_GPU_MAX_LOG2G : s.gpu_log2g; }
+
+inline int choose_log2g(const mck_settings_t &s, size_t len, int width) {
+    if (lg_forced(s)) return forced_lg(s);
+    // CRC-32, 1 KiB to under 8 KiB: 16 steps per payload -- 4 lanes at 1 KiB,
+    // 8 at 2 KiB, 16 at 4 KiB.  Round 6 timed these shapes on cold lines
+    // (4 copies of each batch read in turn, so no launch re-reads what the
+    // last one left in the 256 MiB Infinity Cache; tools/ab_variants.py
+    // --rotate 4, profiles/r06/ab_lgcold.log): C2's 4 KiB at 16 lanes 50.5 us
+    // against 61.6 at 4 (+22%), 2 KiB at 8 lanes +3%; round 4 had chosen 4
+    // lanes throughout from back-to-back replays of one batch, which the
+    // cache served (-1.9% for 16 lanes there).  From 8 KiB about 32 steps
+    // per payload (8 KiB: 16 lanes, 16 KiB: 32 -- both still the best cold),
+    // 64 lanes from 32 KiB (the headline).
+    if (width == 32 && len >= 1024) {
+        if (len < 8192) {
+            int lg = 2;
+            while (lg < 4 && ((size_t)512 << lg) <= len) lg++;
+            return lg;
+        }
+        int lg = 0;
+        while (lg < CRC_GPU_MAX_LOG2G && ((size_t)512 << (lg + 1)) <= len) lg++;
+        return lg;
+    }
+    // CRC-64 (profiles/r04/ab_crc64_log2g.log): about 128 steps per payload,
+    // 4 lanes at least -- 4 KiB: 4 lanes -6.9%, 16 KiB: 8 lanes -6.7%, 64 KiB:
+    // 32 lanes -3.5% against the >= 16-step rule's 16 / 64 / 64.
+    if (width == 64 && len >= 1024) {
+        int lg = 2;
+        while (lg < CRC_GPU_MAX_LOG2G && ((size_t)2048 << (lg + 1)) <= len) lg++;
+        return lg;
+    }
+    // Otherwise aim for >= 16 steps per payload, at most 64 lanes per payload.
+    const size_t target = len / 256;
+    int lg = 0;
+    while (lg < CRC_GPU_MAX_LOG2G && ((size_t)1 << (lg + 1)) <= target) lg++;
+    return lg;
+}
+
+// Small batches (<= 16 MiB) take the light CRC-32C layout (16 KiB LDS fill, 256-thread
+// workgroups over every CU, 64 lanes per payload): the full layout's 140 KiB
+// fill and 1024-thread workgroups cost ~6-12 us per call there
+// (profiles/r01/latency.json).  MCHECKSUM_GPU_LIGHT=0/1 overrides.
+constexpr uint64_t kLightMaxBytes = 16ull << 20;  // crossover ~24 MiB (latency.json)
+inline bool use_light(const mck_settings_t &s, bool small) { return s.gpu_light >= 0 ? s.gpu_light == 1 : small; }
+
+// Lanes per payload for the light layout: as many as keep K >= kRing whole steps.
+inline int light_log2g(const mck_settings_t &s, size_t len) {
+    if (lg_forced(s)) return forced_lg(s);
+    int lg = CRC_GPU_MAX_LOG2G;
+    while (lg > 0 && ((size_t)16 << lg) * kRing > len) lg--;
+    return lg;
+}
+
+// Non-temporal payload loads when the batch is far larger than the 256 MiB
+// Infinity Cache (MCHECKSUM_GPU_NT=0/1 overrides).
+inline bool use_nt(const mck_settings_t &s, bool large) { return s.gpu_nt >= 0 ? s.gpu_nt == 1 : large; }
+inline bool nt_by_bytes(const mck_settings_t &s, uint64_t batch_bytes) { return use_nt(s, batch_bytes >= (512ull << 20)); }
+// Offsets and XDR batches: the offsets table stays on the device, so size the
+// batch by its count: 8192+ payloads of the C4 mix are ~270 MB and up.
+inline bool nt_by_count(const mck_settings_t &s, size_t count) { return use_nt(s, count >= 8192); }
+
+// A receive queue's worth of RPCs: offsets batches up to this many payloads
+// take the light layout, XDR batches past it the throughput layout.
+constexpr size_t kRecvQueueBatch = 1024;
+
+// Large aligned CRC-64 payloads go to the work queue as kSplitBytes pieces
+// (crc64_batch_kernel<..., SPLIT>) once the batch is big enough for the
+// non-temporal path; MCHECKSUM_GPU_SPLIT=0/1 overrides.
+inline bool use_split(const mck_settings_t &s, int width, int lg, bool aligned, bool nt, size_t len, size_t stride) {
+    if (s.gpu_split == 0) return false;
+    const bool shape = width == 64 && lg == CRC_GPU_MAX_LOG2G && aligned && len % kSplitBytes == 0 &&
+                       len / kSplitBytes >= 2 && len / kSplitBytes <= 64 && ((len / kSplitBytes) & (len / kSplitBytes - 1)) == 0 &&
+                       stride % 16 == 0;
+    if (s.gpu_split == 1) return shape;
+    return shape && nt;
+}
+
+// Block size and workgroups per CU of a kernel (Shape<>, crc_gpu_device.h; it
+// does not depend on the lane count).
+inline void plan_shape(LaunchPlan &p) {
+    if (p.light) {
+        p.block = Shape<32, kFixedAligned, true>::block;
+        p.blocks_per_cu = Shape<32, kFixedAligned, true>::blocks_per_cu;
+    } else if (p.width == 64 && p.mode == kOffsets) {
+        p.block = Shape<64, kOffsets>::block;
+        p.blocks_per_cu = Shape<64, kOffsets>::blocks_per_cu;
+    } else {
+        p.block = Shape<32, kFixedAligned>::block;
+        p.blocks_per_cu = Shape<32, kFixedAligned>::blocks_per_cu;
+    }
+}
+
+// Workgroups for p.units waves' worth of work: no more than fit the device at once.
+inline unsigned plan_grid(const LaunchPlan &p, int cus) {
+    const uint64_t wpb = (uint64_t)p.block / 64;
+    uint64_t blocks = (p.units + wpb - 1) / wpb;
+    if (blocks > (uint64_t)cus * p.blocks_per_cu) blocks = (uint64_t)cus * p.blocks_per_cu;
+    return blocks ? (unsigned)blocks : 1u;
+}
+
+// A fixed batch: count payloads of len bytes, stride apart, from base.
+inline LaunchPlan plan_fixed(const mck_settings_t &s, int cus, int width, uintptr_t base, size_t stride, size_t len,
+                             size_t count) {
+    LaunchPlan p;
+    p.width = width;
+    p.light = width == 32 && use_light(s, (uint64_t)len * count <= kLightMaxBytes);
+    if (p.light) {
+        p.lg = light_log2g(s, len);
+        // light layout: no more lanes per payload than give every CU about
+        // four waves (4096 x 4 KiB: 16 lanes -12% against 64; 1024 x 4 KiB
+        // keeps 64, profiles/r04/ab_small_knobs.log)
+        if (!lg_forced(s))
+            while (p.lg > 0 && ((uint64_t)count << (p.lg - 1)) >= (uint64_t)cus * 4 * 64) p.lg--;
+    } else {
+        p.lg = choose_log2g(s, len, width);
+        // a batch too small for the chosen payloads per wave to occupy every wave
+        // slot (16 per CU) gets more lanes per payload: 8192 x 4 KiB at 4 lanes
+        // ran 2x slower than at 64 (profiles/r04/ab_small_knobs.log)
+        if (!lg_forced(s))
+            while (p.lg < CRC_GPU_MAX_LOG2G && ((count + (64u >> p.lg) - 1) >> (6 - p.lg)) < (uint64_t)cus * 16) p.lg++;
+    }
+    const uint64_t step = 16ull << p.lg;
+    // The aligned path needs whole steps and K = len/step a multiple of the
+    // load ring depth; everything else takes the generic path.
+    p.aligned = (base % 16 == 0) && (stride % 16 == 0 || count == 1) && len >= step * kRing &&
+                (len % (step * kRing) == 0) && (len >> (4 + p.lg)) < (1ull << 31) && !s.gpu_force_generic;
+    p.mode = p.aligned ? kFixedAligned : kFixedGeneric;
+    // (only the aligned kernels of the full layout have a non-temporal form)
+    const bool nt = !p.light && nt_by_bytes(s, (uint64_t)len * count);
+    p.nt = nt && p.aligned;
+    while ((kSplitBytes << p.split_log2) < len && p.split_log2 < 63) p.split_log2++;
+    p.split = use_split(s, width, p.lg, p.aligned, nt, len, count > 1 ? stride : 16) &&
+              ((uint64_t)count << p.split_log2) <= kMaxUnits;
+    plan_shape(p);
+    if (p.split) {
+        p.dyn = true;
+        p.units = (uint64_t)count << p.split_log2;
+        p.grid = plan_grid(p, cus);
+        // With a slot and queue chunks of whole payloads the pieces combine in
+        // their workgroup (crc_gpu_device.h, split_lds).  Otherwise they XOR
+        // their terms into out[], zeroed first.  MCHECKSUM_GPU_SPLIT_LDS=0:
+        // always through the zeroed output (tests, A/B).
+        p.split_lds_ok = s.gpu_split_lds != 0 && SplitPlan(count, p.split_log2, p.grid).whole();
+        p.zero_out = !p.split_lds_ok;
+        return p;
+    }
+    p.split_log2 = 0;
+    const uint64_t ppw = 64u >> p.lg;
+    p.dyn = dyn_policy(width, p.mode, nt, p.light);
+    p.units = (count + ppw - 1) / ppw;
+    p.grid = plan_grid(p, cus);
+    // CRC-64 static split with fewer units than one full workgroup per CU:
+    // one workgroup per unit, at most one per CU (each pays a 66 KiB LDS
+    // fill); the kernel then numbers waves across workgroups first
+    if (width == 64 && !p.dyn && p.units < (uint64_t)cus * (uint64_t)(p.block / 64))
+        p.grid = (unsigned)(p.units < (uint64_t)cus ? (p.units ? p.units : 1) : cus);
+    return p;
+}
+
+// An offsets, verify or message batch of count payloads: 64 lanes per payload.
+inline LaunchPlan plan_offsets(const mck_settings_t &s, int cus, int width, size_t count) {
+    LaunchPlan p;
+    p.width = width;
+    p.lg = CRC_GPU_MAX_LOG2G;
+    p.mode = kOffsets;
+    // small offsets batches take the light layout
+    p.light = width == 32 && use_light(s, count <= kRecvQueueBatch);
+    const bool nt = nt_by_count(s, count);
+    p.nt = nt && !p.light;  // (the light kernels have no non-temporal form)
+    p.dyn = dyn_policy(width, kOffsets, nt, p.light);
+    p.units = count;
+    plan_shape(p);
+    p.grid = plan_grid(p, cus);
+    return p;
+}
+
+}  // namespace mck
+
+#endif  // MCK_LAUNCH_PLAN_H

@@ -29,6 +29,12 @@
 //    all offsets batches) or by a static stride (crc_gpu_device.h, dyn_policy).
 //    Batches <= 16 MiB take a light layout: unreplicated tables, 256-thread
 //    workgroups on every CU.
+//  * Host side: each entry point validates its arguments, resolves the method
+//    once (resolve_model), takes the device context, decides the whole launch
+//    in one pure plan from one settings snapshot (launch_plan.h: plan_fixed,
+//    plan_offsets), fetches the table pack for the plan's lane count, looks
+//    the kernel up from the plan (kernel_for) and launches it with its
+//    work-queue slot, if the plan takes one (gpu_host.h: launch_slot).
 // No MFMA: this is HBM-bound byte scanning; the roofline is HBM read bandwidth.
 #include <hip/hip_runtime.h>
 
@@ -41,6 +47,7 @@
 
 #include "crc_gpu_device.h"
 #include "gpu_host.h"
+#include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
 
@@ -68,17 +75,22 @@ int hip_err(hipError_t e, const char *what) {
 std::mutex g_mu;
 DevCtx g_dev[kMaxDev];
 
-// Method -> (model index, width) for GPU-capable (32/64-bit) models.
-int gpu_model(const char *method, int *width) {
+// Method -> model for GPU-capable (32/64-bit) models.
+int gpu_model(const char *method, Model *out) {
     const int idx = mck_model_index(method);
     if (idx < 0) return -1;
     const mck_model_t &m = mck_models[idx];
     if (m.width != 32 && m.width != 64) return -2;
-    *width = m.width;
-    return idx;
+    *out = Model{idx, m.width, !m.reflected};
+    return 0;
 }
 
-bool gpu_msb(int idx) { return !mck_models[idx].reflected; }
+int resolve_model(const char *method, Model *out) {
+    const int r = gpu_model(method, out);
+    if (r == -1) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", method ? method : "(null)");
+    if (r < 0) return set_err(MCHECKSUM_GPU_EMETHOD, "method \"%s\" has no GPU kernel (32/64-bit only)", method);
+    return MCHECKSUM_GPU_OK;
+}
 
 // A reflected model as is; an MSB-first model as the reflected model of the
 // same polynomial over bit-reversed bytes, conjugated by R (crc_gpu_layout.h):
@@ -106,12 +118,16 @@ __global__ __launch_bounds__(256) void bswap_kernel(void *out, uint64_t n, int w
     }
 }
 
+// Grid of the 256-thread element kernels (bswap_kernel, zero_u64_kernel): they stride past 1024 workgroups.
+unsigned elem_grid(uint64_t n) {
+    const uint64_t blocks = (n + 255) / 256;
+    return blocks > 1024 ? 1024u : (unsigned)blocks;
+}
+
 int swap_outputs(void *dev_out, uint64_t count, int width, void *stream) {
     if (!count) return MCHECKSUM_GPU_OK;
-    uint64_t blocks = (count + 255) / 256;
-    blocks = blocks > 1024 ? 1024 : blocks;
     const hipError_t e =
-        launch_kernel(bswap_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, nullptr, dev_out, count, width);
+        launch_kernel(bswap_kernel, dim3(elem_grid(count)), dim3(256), (hipStream_t)stream, nullptr, dev_out, count, width);
     if (e != hipSuccess) return hip_err(e, "output byte swap");
     return MCHECKSUM_GPU_OK;
 }
@@ -323,140 +339,56 @@ struct KLaunch {
     int block, blocks_per_cu;
 };
 
-// MCHECKSUM_GPU_LOG2G=g: 2^g lanes per payload for every fixed batch (A/B)
-bool lg_forced() { return mck_settings()->gpu_log2g >= 0; }
-
-int choose_log2g(size_t len, int width) {
-    if (lg_forced()) return mck_settings()->gpu_log2g;
-    // CRC-32, 1 KiB to under 8 KiB: 16 steps per payload -- 4 lanes at 1 KiB,
-    // 8 at 2 KiB, 16 at 4 KiB.  Round 6 timed these shapes on cold lines
-    // (4 copies of each batch read in turn, so no launch re-reads what the
-    // last one left in the 256 MiB Infinity Cache; tools/ab_variants.py
-    // --rotate 4, profiles/r06/ab_lgcold.log): C2's 4 KiB at 16 lanes 50.5 us
-    // against 61.6 at 4 (+22%), 2 KiB at 8 lanes +3%; round 4 had chosen 4
-    // lanes throughout from back-to-back replays of one batch, which the
-    // cache served (-1.9% for 16 lanes there).  From 8 KiB about 32 steps
-    // per payload (8 KiB: 16 lanes, 16 KiB: 32 -- both still the best cold),
-    // 64 lanes from 32 KiB (the headline).
-    if (width == 32 && len >= 1024) {
-        if (len < 8192) {
-            int lg = 2;
-            while (lg < 4 && ((size_t)512 << lg) <= len) lg++;
-            return lg;
-        }
-        int lg = 0;
-        while (lg < CRC_GPU_MAX_LOG2G && ((size_t)512 << (lg + 1)) <= len) lg++;
-        return lg;
-    }
-    // CRC-64 (profiles/r04/ab_crc64_log2g.log): about 128 steps per payload,
-    // 4 lanes at least -- 4 KiB: 4 lanes -6.9%, 16 KiB: 8 lanes -6.7%, 64 KiB:
-    // 32 lanes -3.5% against the >= 16-step rule's 16 / 64 / 64.
-    if (width == 64 && len >= 1024) {
-        int lg = 2;
-        while (lg < CRC_GPU_MAX_LOG2G && ((size_t)2048 << (lg + 1)) <= len) lg++;
-        return lg;
-    }
-    // Otherwise aim for >= 16 steps per payload, at most 64 lanes per payload.
-    const size_t target = len / 256;
-    int lg = 0;
-    while (lg < CRC_GPU_MAX_LOG2G && ((size_t)1 << (lg + 1)) <= target) lg++;
-    return lg;
-}
-
-template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false>
+template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false, bool SPLIT = false>
 KLaunch kernel_ptr() {
     using S = Shape<W, MODE, LIGHT, LOG2G>;
     if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT>, S::block, S::blocks_per_cu};
-    else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT>, S::block, S::blocks_per_cu};
-}
-
-template <int W, int LOG2G>
-KLaunch pick_fixed_lg(bool aligned, bool nt, bool light) {
-    if constexpr (W == 32) {
-        if (light)
-            return aligned ? kernel_ptr<W, LOG2G, kFixedAligned, false, false, true>()
-                           : kernel_ptr<W, LOG2G, kFixedGeneric, false, false, true>();
-    }
-    if (!aligned) return kernel_ptr<W, LOG2G, kFixedGeneric, false>();
-    return nt ? kernel_ptr<W, LOG2G, kFixedAligned, false, true>() : kernel_ptr<W, LOG2G, kFixedAligned, false>();
+    else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT>, S::block, S::blocks_per_cu};
 }
 
 template <int W>
-KLaunch pick_fixed(int log2g, bool aligned, bool nt, bool light) {
-    switch (log2g) {
-        case 0: return pick_fixed_lg<W, 0>(aligned, nt, light);
-        case 1: return pick_fixed_lg<W, 1>(aligned, nt, light);
-        case 2: return pick_fixed_lg<W, 2>(aligned, nt, light);
-        case 3: return pick_fixed_lg<W, 3>(aligned, nt, light);
-        case 4: return pick_fixed_lg<W, 4>(aligned, nt, light);
-        case 5: return pick_fixed_lg<W, 5>(aligned, nt, light);
-        default: return pick_fixed_lg<W, 6>(aligned, nt, light);
+KLaunch offsets_kernel(const LaunchPlan &p, bool verify) {
+    if constexpr (W == 32) {
+        if (p.light)
+            return verify ? kernel_ptr<W, 6, kOffsets, true, false, true>() : kernel_ptr<W, 6, kOffsets, false, false, true>();
+    }
+    if (verify) return p.nt ? kernel_ptr<W, 6, kOffsets, true, true>() : kernel_ptr<W, 6, kOffsets, true>();
+    return p.nt ? kernel_ptr<W, 6, kOffsets, false, true>() : kernel_ptr<W, 6, kOffsets, false>();
+}
+
+template <int W, int LOG2G>
+KLaunch fixed_kernel_lg(const LaunchPlan &p) {
+    if constexpr (W == 32) {
+        if (p.light)
+            return p.aligned ? kernel_ptr<W, LOG2G, kFixedAligned, false, false, true>()
+                             : kernel_ptr<W, LOG2G, kFixedGeneric, false, false, true>();
+    }
+    if (!p.aligned) return kernel_ptr<W, LOG2G, kFixedGeneric, false>();
+    return p.nt ? kernel_ptr<W, LOG2G, kFixedAligned, false, true>() : kernel_ptr<W, LOG2G, kFixedAligned, false>();
+}
+
+template <int W>
+KLaunch fixed_kernel(const LaunchPlan &p) {
+    switch (p.lg) {
+        case 0: return fixed_kernel_lg<W, 0>(p);
+        case 1: return fixed_kernel_lg<W, 1>(p);
+        case 2: return fixed_kernel_lg<W, 2>(p);
+        case 3: return fixed_kernel_lg<W, 3>(p);
+        case 4: return fixed_kernel_lg<W, 4>(p);
+        case 5: return fixed_kernel_lg<W, 5>(p);
+        default: return fixed_kernel_lg<W, 6>(p);
     }
 }
 
-// Non-temporal payload loads when the batch is far larger than the 256 MiB
-// Infinity Cache (MCHECKSUM_GPU_NT=0/1 overrides).
-// Small batches (<= 16 MiB) take the light CRC-32C layout (16 KiB LDS fill, 256-thread
-// workgroups over every CU, 64 lanes per payload): the full layout's 140 KiB
-// fill and 1024-thread workgroups cost ~6-12 us per call there
-// (profiles/r01/latency.json).  MCHECKSUM_GPU_LIGHT=0/1 overrides.
-constexpr uint64_t kLightMaxBytes = 16ull << 20;  // crossover ~24 MiB (latency.json)
-bool use_light(uint64_t batch_bytes, bool known) {
-    if (mck_settings()->gpu_light >= 0) return mck_settings()->gpu_light == 1;
-    return known && batch_bytes <= kLightMaxBytes;
+// The kernel a plan (launch_plan.h) launches; verify: it compares with the
+// expected values instead of storing its own.
+KLaunch kernel_for(const LaunchPlan &p, bool verify) {
+    if (p.mode == kOffsets) return p.width == 32 ? offsets_kernel<32>(p, verify) : offsets_kernel<64>(p, verify);
+    if (p.split)
+        return p.nt ? kernel_ptr<64, 6, kFixedAligned, false, true, false, true>()
+                    : kernel_ptr<64, 6, kFixedAligned, false, false, false, true>();
+    return p.width == 32 ? fixed_kernel<32>(p) : fixed_kernel<64>(p);
 }
-
-// Lanes per payload for the light layout: as many as keep K >= kRing whole steps.
-int light_log2g(size_t len) {
-    if (lg_forced()) return mck_settings()->gpu_log2g;
-    int lg = CRC_GPU_MAX_LOG2G;
-    while (lg > 0 && ((size_t)16 << lg) * kRing > len) lg--;
-    return lg;
-}
-
-bool use_nt(uint64_t batch_bytes) {
-    if (mck_settings()->gpu_nt >= 0) return mck_settings()->gpu_nt == 1;
-    return batch_bytes >= (512ull << 20);
-}
-
-// Launch a batch kernel; a slot launch records the slot's completion event.
-// A failed launch call is taken back from its slot (slot_unissue).
-int launch(DevCtx *c, const KLaunch &kl, const BatchArgs &a, unsigned blocks, void *stream, SlotRef &sr) {
-    const hipError_t e = launch_kernel(kl.k, dim3(blocks), dim3(kl.block), (hipStream_t)stream, sr.done, a);
-    if (e != hipSuccess) {
-        slot_unissue(c, sr);
-        return hip_err(e, "kernel launch");
-    }
-    slot_issued(sr);
-    return MCHECKSUM_GPU_OK;
-}
-
-unsigned grid_for(const DevCtx *c, uint64_t waves_needed, const KLaunch &kl) {
-    const uint64_t wpb = (uint64_t)kl.block / 64;
-    uint64_t blocks = (waves_needed + wpb - 1) / wpb;
-    if (blocks > (uint64_t)c->cus * kl.blocks_per_cu) blocks = (uint64_t)c->cus * kl.blocks_per_cu;
-    return blocks ? (unsigned)blocks : 1u;
-}
-
-// The table pack for another lanes-per-payload choice (cached per device).
-int repack(DevCtx *c, const char *method, int log2g, const void **pack) {
-    int width = 0;
-    const int idx = gpu_model(method, &width);
-    return get_pack(c, idx, log2g, pack);
-}
-
-int prologue(const char *method, int log2g, int *width, DevCtx **c, const void **pack) {
-    int idx = gpu_model(method, width);
-    if (idx == -1) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", method ? method : "(null)");
-    if (idx < 0) return set_err(MCHECKSUM_GPU_EMETHOD, "method \"%s\" has no GPU kernel (32/64-bit only)", method);
-    int rc = device_ctx(c);
-    if (rc) return rc;
-    return get_pack(*c, idx, log2g, pack);
-}
-
-// The work queue counts chunk ids and per-workgroup slots in 32 bits
-// (crc_gpu_device.h, WgQueue): 2^31 payloads per call keeps both in range.
-constexpr uint64_t kMaxUnits = 1ull << 31;
 
 int do_offsets(const char *method, const void *base, const uint64_t *offsets, size_t count, void *out,
                const void *expected, uint8_t *status, uint32_t *mism, void *stream, bool verify,
@@ -468,12 +400,17 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
     if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
-    int width = 0;
+    Model m;
     DevCtx *c = nullptr;
     const void *pack = nullptr;
-    int rc = prologue(method, CRC_GPU_MAX_LOG2G, &width, &c, &pack);
+    int rc = resolve_model(method, &m);
+    if (!rc) rc = device_ctx(&c);
     if (rc) return rc;
+    const LaunchPlan p = plan_offsets(*mck_settings(), c->cus, m.width, count);
+    if ((rc = get_pack(c, m.idx, p.lg, &pack))) return rc;
     if (count == 0) return MCHECKSUM_GPU_OK;
+    if (msg && m.width != 32)
+        return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
     BatchArgs a{};
     a.base = (const uint8_t *)base;
     a.offsets = offsets;
@@ -486,60 +423,19 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
     a.msg = msg ? 1u : 0u;
     a.pay_off = (uint32_t)pay_off;
     a.hash_off = (uint32_t)hash_off;
-    a.queue = nullptr;
     a.err_word = t_err_word;
-    if (msg && width != 32)
-        return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const int midx = gpu_model(method, &width);
-    a.bswap = verify && gpu_msb(midx) ? 1u : 0u;  // checksum calls swap after the launch
-    KLaunch k;
-    // The offsets table stays on the device, so size the batch by its count:
-    // 8192+ payloads of the C4 mix are ~270 MB and up.
-    const bool nt = use_nt(count >= 8192 ? (1ull << 40) : 0);
-    // small offsets batches (<= 1024 payloads: a receive queue's worth of RPCs)
-    // take the light layout
-    const bool light = width == 32 && use_light(count <= 1024 ? 0 : ~0ull, true);
-    if (width == 32 && light)
-        k = verify ? kernel_ptr<32, 6, kOffsets, true, false, true>() : kernel_ptr<32, 6, kOffsets, false, false, true>();
-    else if (width == 32)
-        k = verify ? (nt ? kernel_ptr<32, 6, kOffsets, true, true>() : kernel_ptr<32, 6, kOffsets, true>())
-                   : (nt ? kernel_ptr<32, 6, kOffsets, false, true>() : kernel_ptr<32, 6, kOffsets, false>());
-    else
-        k = verify ? (nt ? kernel_ptr<64, 6, kOffsets, true, true>() : kernel_ptr<64, 6, kOffsets, true>())
-                   : (nt ? kernel_ptr<64, 6, kOffsets, false, true>() : kernel_ptr<64, 6, kOffsets, false>());
+    a.bswap = verify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
+    const KLaunch k = kernel_for(p, verify);
     SlotRef sr;
-    const unsigned grid = grid_for(c, count, k);
-    if (dyn_policy(width, kOffsets, nt, light)) sr = queue_slot(c, stream);
+    if (p.dyn) sr = queue_slot(c, stream);
     a.queue = sr.q;
-    rc = launch(c, k, a, grid, stream, sr);
-    if (rc == MCHECKSUM_GPU_OK && gpu_msb(midx) && !verify) rc = swap_outputs(out, count, width, stream);
+    rc = launch_slot(c, sr, k.k, p.grid, k.block, stream, a, "kernel launch");
+    if (rc == MCHECKSUM_GPU_OK && m.msb && !verify) rc = swap_outputs(out, count, m.width, stream);
     return rc;
 }
 
-// Large aligned CRC-64 payloads go to the work queue as kSplitBytes pieces
-// (crc64_batch_kernel<..., SPLIT>) once the batch is big enough for the
-// non-temporal path; MCHECKSUM_GPU_SPLIT=0/1 overrides.
-bool use_split(int width, int lg, bool aligned, bool nt, size_t len, size_t stride) {
-    const int forced = mck_settings()->gpu_split;
-    if (forced == 0) return false;
-    const bool shape = width == 64 && lg == CRC_GPU_MAX_LOG2G && aligned && len % kSplitBytes == 0 &&
-                       len / kSplitBytes >= 2 && len / kSplitBytes <= 64 && ((len / kSplitBytes) & (len / kSplitBytes - 1)) == 0 &&
-                       stride % 16 == 0;
-    if (forced == 1) return shape;
-    return shape && nt;
-}
-
-// MCHECKSUM_GPU_SPLIT_LDS=0: split CRC-64 pieces always combine through the
-// zeroed output (tests, A/B).
-bool use_split_lds() { return mck_settings()->gpu_split_lds != 0; }
-
-int launch_fixed(DevCtx *c, int idx, const void *pack, int width, int lg, const void *dev_base, size_t stride,
-                 size_t len, size_t count, void *dev_out, void *stream, bool light) {
-    const uint64_t step = 16ull << lg;
-    // The aligned path needs whole steps and K = len/step a multiple of the
-    // load ring depth; everything else takes the generic path.
-    const bool aligned = ((uintptr_t)dev_base % 16 == 0) && (stride % 16 == 0 || count == 1) &&
-                         len >= step * kRing && (len % (step * kRing) == 0) && (len >> (4 + lg)) < (1ull << 31) && !mck_settings()->gpu_force_generic;
+int launch_fixed(DevCtx *c, const Model &m, const LaunchPlan &p, const void *pack, const void *dev_base, size_t stride,
+                 size_t len, size_t count, void *dev_out, void *stream) {
     BatchArgs a{};
     a.base = (const uint8_t *)dev_base;
     a.stride = stride;
@@ -548,58 +444,33 @@ int launch_fixed(DevCtx *c, int idx, const void *pack, int width, int lg, const 
     a.out = dev_out;
     a.pack = pack;
     a.err_word = t_err_word;
-    const bool nt = !light && use_nt((uint64_t)len * count);
-    uint32_t sl = 0;
-    while ((kSplitBytes << sl) < len && sl < 63) sl++;
-    if (use_split(width, lg, aligned, nt, len, count > 1 ? stride : 16) && ((uint64_t)count << sl) <= kMaxUnits) {
+    if (p.split) {
         const void *shift = nullptr;
-        if (int rc = get_ext(c, idx, &shift)) return rc;
+        if (int rc = get_ext(c, m.idx, &shift)) return rc;
         a.shift = shift;
-        a.split_log2 = sl;
-        using S6 = Shape<64, kFixedAligned, false, 6>;
-        const KLaunch k = nt ? KLaunch{crc64_batch_kernel<6, kFixedAligned, false, true, true>, S6::block, S6::blocks_per_cu}
-                             : KLaunch{crc64_batch_kernel<6, kFixedAligned, false, false, true>, S6::block, S6::blocks_per_cu};
-        const unsigned grid = grid_for(c, (uint64_t)count << sl, k);
-        SlotRef sr = queue_slot(c, stream);
-        a.queue = sr.q;
-        // With a slot and queue chunks of whole payloads the pieces combine in
-        // their workgroup (crc_gpu_device.h, split_lds).  Otherwise they XOR
-        // their terms into out[]: zero it first, in stream order, with a kernel
-        // -- a hipMemsetAsync captured into a graph did not order against the
-        // kernel node on replays after the first (the pieces landed in a
-        // half-zeroed output: tests/test_gpu_queue.py, concurrent replays).
-        a.split_lds = sr.q && use_split_lds() && SplitPlan(count, sl, grid).whole() ? 1u : 0u;
-        if (!a.split_lds) {
-            uint64_t zb = (count + 255) / 256;
-            zb = zb > 1024 ? 1024 : zb;
-            const hipError_t e = launch_kernel(zero_u64_kernel, dim3((unsigned)zb), dim3(256), (hipStream_t)stream, nullptr,
-                                               reinterpret_cast<unsigned long long *>(dev_out), (uint64_t)count);
-            if (e != hipSuccess) {
-                slot_unissue(c, sr);
-                return hip_err(e, "output zeroing");
-            }
-        }
-        int rc = launch(c, k, a, grid, stream, sr);
-        if (rc == MCHECKSUM_GPU_OK && gpu_msb(idx)) rc = swap_outputs(dev_out, count, width, stream);
-        return rc;
+        a.split_log2 = p.split_log2;
     }
-    const KLaunch k = width == 32 ? pick_fixed<32>(lg, aligned, nt, light) : pick_fixed<64>(lg, aligned, nt, false);
-    const uint64_t ppw = 64u >> lg;
-    const bool dyn = dyn_policy(width, aligned ? kFixedAligned : kFixedGeneric, nt, light);
-    const uint64_t units = (count + ppw - 1) / ppw;
-    unsigned blocks = grid_for(c, units, k);
-    // CRC-64 static split with fewer units than one full workgroup per CU:
-    // one workgroup per unit, at most one per CU (each pays a 66 KiB LDS
-    // fill); the kernel then numbers waves across workgroups first
-    if (width == 64 && !dyn && units < (uint64_t)c->cus * (uint64_t)(k.block / 64))
-        blocks = (unsigned)(units < (uint64_t)c->cus ? (units ? units : 1) : c->cus);
+    const KLaunch k = kernel_for(p, false);
     SlotRef sr;
-    if (dyn) {
-        sr = queue_slot(c, stream);
-        a.queue = sr.q;
+    if (p.dyn) sr = queue_slot(c, stream);
+    a.queue = sr.q;
+    // Split pieces that cannot combine in their workgroup (no slot, or chunks
+    // of part payloads: launch_plan.h) XOR their terms into out[]: zero it
+    // first, in stream order, with a kernel -- a hipMemsetAsync captured into
+    // a graph did not order against the kernel node on replays after the
+    // first (the pieces landed in a half-zeroed output:
+    // tests/test_gpu_queue.py, concurrent replays).
+    a.split_lds = sr.q && p.split_lds_ok ? 1u : 0u;
+    if (p.split && (p.zero_out || !sr.q)) {
+        const hipError_t e = launch_kernel(zero_u64_kernel, dim3(elem_grid(count)), dim3(256), (hipStream_t)stream, nullptr,
+                                           reinterpret_cast<unsigned long long *>(dev_out), (uint64_t)count);
+        if (e != hipSuccess) {
+            slot_unissue(c, sr);
+            return hip_err(e, "output zeroing");
+        }
     }
-    int rc = launch(c, k, a, blocks, stream, sr);
-    if (rc == MCHECKSUM_GPU_OK && gpu_msb(idx)) rc = swap_outputs(dev_out, count, width, stream);
+    int rc = launch_slot(c, sr, k.k, p.grid, k.block, stream, a, "kernel launch");
+    if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(dev_out, count, m.width, stream);
     return rc;
 }
 
@@ -630,27 +501,24 @@ int mchecksum_gpu_prepare(const char *hash_method) {
     const int idx = mck_model_index(hash_method);
     if (idx < 0) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", hash_method ? hash_method : "(null)");
     DevCtx *c = nullptr;
-    if (mck_models[idx].width != 16) {  // payload kernels: a table pack per lanes-per-payload width
-        for (int lg = 0; lg <= CRC_GPU_MAX_LOG2G; lg++) {
-            int width = 0;
-            const void *pack = nullptr;
-            int rc = prologue(hash_method, lg, &width, &c, &pack);
-            if (rc) return rc;
-        }
+    int rc = device_ctx(&c);
+    // payload kernels (32/64-bit models): a table pack per lanes-per-payload width
+    for (int lg = 0; mck_models[idx].width != 16 && !rc && lg <= CRC_GPU_MAX_LOG2G; lg++) {
+        const void *pack = nullptr;
+        rc = get_pack(c, idx, lg, &pack);
     }
+    if (rc) return rc;
     // ... and the extension tables every entry point may need (Z^n shift pack:
     // split CRC-64 pieces, segments, XDR; CRC-16 byte table: core headers),
     // so that no call captured into a graph uploads anything
-    int rc = device_ctx(&c);
-    if (rc) return rc;
     const void *ext = nullptr;
     return get_ext(c, idx, &ext);
 }
 
 int mchecksum_gpu_lanes_per_payload(const char *hash_method, size_t len) {
-    int width = 0;
-    if (gpu_model(hash_method, &width) < 0) return -1;
-    return 1 << choose_log2g(len, width);
+    Model m;
+    if (gpu_model(hash_method, &m) < 0) return -1;
+    return 1 << choose_log2g(*mck_settings(), len, m.width);
 }
 
 int mchecksum_gpu_checksum_fixed(const char *hash_method, const void *dev_base, size_t stride, size_t len,
@@ -662,40 +530,16 @@ int mchecksum_gpu_checksum_fixed(const char *hash_method, const void *dev_base, 
     if (count > 1 && (uint64_t)stride > (UINT64_MAX - (uint64_t)len) / (count - 1))
         return set_err(MCHECKSUM_GPU_EINVAL, "stride * (count - 1) + len overflows");
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
-    int width = 0;
-    if (gpu_model(hash_method, &width) >= 0 && width == 32 && use_light((uint64_t)len * count, true)) {
-        int lg = light_log2g(len);
-        DevCtx *c = nullptr;
-        const void *pack = nullptr;
-        int rc = prologue(hash_method, lg, &width, &c, &pack);
-        if (rc) return rc;
-        if (count == 0) return MCHECKSUM_GPU_OK;
-        // light layout: no more lanes per payload than give every CU about
-        // four waves (4096 x 4 KiB: 16 lanes -12% against 64; 1024 x 4 KiB
-        // keeps 64, profiles/r04/ab_small_knobs.log)
-        const int lg0 = lg;
-        if (!lg_forced())
-            while (lg > 0 && ((uint64_t)count << (lg - 1)) >= (uint64_t)c->cus * 4 * 64) lg--;
-        if (lg != lg0 && (rc = repack(c, hash_method, lg, &pack))) return rc;
-        return launch_fixed(c, gpu_model(hash_method, &width), pack, width, lg, dev_base, stride, len, count, dev_out,
-                            stream, true);
-    }
-    int lg = choose_log2g(len, width);
+    Model m;
     DevCtx *c = nullptr;
     const void *pack = nullptr;
-    int rc = prologue(hash_method, lg, &width, &c, &pack);
+    int rc = resolve_model(hash_method, &m);
+    if (!rc) rc = device_ctx(&c);
     if (rc) return rc;
+    const LaunchPlan p = plan_fixed(*mck_settings(), c->cus, m.width, (uintptr_t)dev_base, stride, len, count);
+    if ((rc = get_pack(c, m.idx, p.lg, &pack))) return rc;
     if (count == 0) return MCHECKSUM_GPU_OK;
-    // a batch too small for the chosen payloads per wave to occupy every wave
-    // slot (16 per CU) gets more lanes per payload: 8192 x 4 KiB at 4 lanes
-    // ran 2x slower than at 64 (profiles/r04/ab_small_knobs.log)
-    const int lg0 = lg;
-    if (!lg_forced())
-        while (lg < CRC_GPU_MAX_LOG2G && ((count + (64u >> lg) - 1) >> (6 - lg)) < (uint64_t)c->cus * 16) lg++;
-    // (the pack for another width only: repack)
-    if (lg != lg0 && (rc = repack(c, hash_method, lg, &pack))) return rc;
-    return launch_fixed(c, gpu_model(hash_method, &width), pack, width, lg, dev_base, stride, len, count, dev_out,
-                        stream, false);
+    return launch_fixed(c, m, p, pack, dev_base, stride, len, count, dev_out, stream);
 }
 
 int mchecksum_gpu_checksum_offsets(const char *hash_method, const void *dev_base, const uint64_t *dev_offsets,
@@ -753,31 +597,18 @@ int mchecksum_gpu_queue_stats(long long *stats, size_t n) {
 }
 
 #if MCK_TRACE
-// Diagnostic builds only: copy the per-wave stamps of the last launch.
-MCHECKSUM_PUBLIC int mck_debug_trace_read(void *host, size_t bytes) {
-    if (bytes > sizeof(g_mck_trace)) bytes = sizeof(g_mck_trace);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mck_trace), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-// ... the per-wave work-queue timings of the last launch ...
-MCHECKSUM_PUBLIC int mck_debug_qwave_read(void *host, size_t bytes) {
-    if (bytes > sizeof(g_mck_qwave)) bytes = sizeof(g_mck_qwave);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mck_qwave), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-// ... the per-unit completion stamps of the last launch ...
-MCHECKSUM_PUBLIC int mck_debug_units_read(void *host, size_t bytes) {
-    if (bytes > sizeof(g_mck_unit_end)) bytes = sizeof(g_mck_unit_end);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mck_unit_end), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-// ... the XCD of each wave of the last launch ...
-MCHECKSUM_PUBLIC int mck_debug_trace_xcc_read(void *host, size_t bytes) {
-    if (bytes > sizeof(g_mck_trace_xcc)) bytes = sizeof(g_mck_trace_xcc);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mck_trace_xcc), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-// ... the shader-clock stamps (entry, exit) of each wave of the last launch ...
-MCHECKSUM_PUBLIC int mck_debug_trace_clk_read(void *host, size_t bytes) {
-    if (bytes > sizeof(g_mck_trace_clk)) bytes = sizeof(g_mck_trace_clk);
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mck_trace_clk), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
+// Diagnostic builds only: copy what the last launch left in a device symbol.
+#define MCK_DEBUG_READ(name, sym)                                                                                     \
+    MCHECKSUM_PUBLIC int name(void *host, size_t bytes) {                                                             \
+        if (bytes > sizeof(sym)) bytes = sizeof(sym);                                                                 \
+        return hipMemcpyFromSymbol(host, HIP_SYMBOL(sym), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;    \
+    }
+MCK_DEBUG_READ(mck_debug_trace_read, g_mck_trace)          // the per-wave stamps
+MCK_DEBUG_READ(mck_debug_qwave_read, g_mck_qwave)          // the per-wave work-queue timings
+MCK_DEBUG_READ(mck_debug_units_read, g_mck_unit_end)       // the per-unit completion stamps
+MCK_DEBUG_READ(mck_debug_trace_xcc_read, g_mck_trace_xcc)  // the XCD of each wave
+MCK_DEBUG_READ(mck_debug_trace_clk_read, g_mck_trace_clk)  // the shader-clock stamps (entry, exit) of each wave
+#undef MCK_DEBUG_READ
 // ... and the work-queue fault records (count, then 4 words per record).
 MCHECKSUM_PUBLIC int mck_debug_qdiag_read(unsigned int *n, unsigned long long *rec) {
     if (hipMemcpyFromSymbol(n, HIP_SYMBOL(g_mck_qdiag_n), sizeof(*n), 0, hipMemcpyDeviceToHost) != hipSuccess) return -1;

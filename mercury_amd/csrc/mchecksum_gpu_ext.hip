@@ -29,6 +29,7 @@
 
 #include "crc_gpu_device.h"
 #include "gpu_host.h"
+#include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
 
@@ -1094,13 +1095,15 @@ int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev
     if (work_size < mchecksum_gpu_segments_work_size(nseg) || (uintptr_t)dev_work % 8)
         return set_err(MCHECKSUM_GPU_EINVAL, "workspace smaller than mchecksum_gpu_segments_work_size() or unaligned");
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
-    int width = 0;
+    Model m;
     DevCtx *c = nullptr;
     const void *pack = nullptr, *shift = nullptr;
-    int rc = prologue(hash_method, CRC_GPU_MAX_LOG2G, &width, &c, &pack);
+    int rc = resolve_model(hash_method, &m);
+    if (!rc) rc = device_ctx(&c);
+    if (!rc) rc = get_pack(c, m.idx, CRC_GPU_MAX_LOG2G, &pack);
+    if (!rc) rc = get_ext(c, m.idx, &shift);
     if (rc) return rc;
-    rc = get_ext(c, mck_model_index(hash_method), &shift);
-    if (rc) return rc;
+    const int width = m.width;
     if (nobj == 0) return MCHECKSUM_GPU_OK;
     hipStream_t s = (hipStream_t)stream;
     SegArgs a{};
@@ -1132,7 +1135,7 @@ int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev
     // every object starts as the CRC of the empty message, init ^ xorout in
     // the kernels' register form (MSB-first models: byte-reversed, swapped
     // back with the outputs below)
-    const crc_rmodel_t rm = gpu_rmodel(mck_model_index(hash_method));
+    const crc_rmodel_t rm = gpu_rmodel(m.idx);
     const uint64_t preset = rm.rinit ^ rm.xorout;
     ScanArgs sa{};
     sa.len = dev_seg_len;
@@ -1157,22 +1160,14 @@ int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev
     sa.fault_block = scan_fault_block();
     hipError_t e = launch_kernel(seg_scan, dim3((unsigned)nb), dim3(kScanThreads), s, nullptr, sa);
     if (e != hipSuccess) return hip_err(e, "segment scan launch");
-    if (width == 32) {
-        e = launch_kernel(seg_kernel<32>, dim3(c->cus), dim3(1024), s, nullptr, a);
-        if (e != hipSuccess) return hip_err(e, "segment kernel launch");
-    } else {
-        SlotRef sr = queue_slot(c, stream);
-        a.queue = sr.q;
-        e = launch_kernel(seg_kernel<64>, dim3(c->cus), dim3(1024), s, sr.done, a);
-        if (e != hipSuccess) {
-            slot_unissue(c, sr);
-            return hip_err(e, "segment kernel launch");
-        }
-        slot_issued(sr);
-    }
+    SlotRef sr;  // only the CRC-64 pass takes chunks from a work queue
+    if (width == 64) sr = queue_slot(c, stream);
+    a.queue = sr.q;
+    rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, stream, a,
+                     "segment kernel launch");
     // MSB-first model: the kernels' values are the CRCs byte-swapped (crc_gpu_layout.h)
-    if (gpu_msb(mck_model_index(hash_method))) return swap_outputs(dev_out, nobj, width, stream);
-    return MCHECKSUM_GPU_OK;
+    if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(dev_out, nobj, width, stream);
+    return rc;
 }
 
 int mchecksum_gpu_verify_core_headers(const char *hash_method, int kind, const void *dev_buf,
@@ -1228,12 +1223,13 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
         a.kind[f] = k;
         a.size[f] = z;
     }
-    int width = 0;
-    const int idx = gpu_model(hash_method, &width);
-    if (idx == -1) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", hash_method ? hash_method : "(null)");
-    if (idx < 0 || gpu_msb(idx))
+    Model model;
+    const int found = gpu_model(hash_method, &model);
+    if (found == -1) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", hash_method ? hash_method : "(null)");
+    if (found < 0 || model.msb)
         return set_err(MCHECKSUM_GPU_EMETHOD, "method \"%s\" has no XDR kernel (reflected 32/64-bit only)", hash_method);
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    const int idx = model.idx, width = model.width;
     DevCtx *c = nullptr;
     const void *shift = nullptr;
     if (int rc = device_ctx(&c)) return rc;
@@ -1241,13 +1237,11 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
     if (count == 0) return MCHECKSUM_GPU_OK;
     // throughput layout for batches past a receive queue's worth of RPCs
     // (MCHECKSUM_GPU_XDR_FAST=0/1 overrides)
-    const int fset = mck_settings()->gpu_xdr_fast;
-    const bool fast = fset >= 0 ? fset == 1 : count > 1024;
+    const mck_settings_t &s = *mck_settings();
+    const bool fast = s.gpu_xdr_fast >= 0 ? s.gpu_xdr_fast == 1 : count > kRecvQueueBatch;
     if (fast) {
-        int w2 = 0;
         const void *pack = nullptr;
-        int rc = prologue(hash_method, CRC_GPU_MAX_LOG2G, &w2, &c, &pack);
-        if (rc) return rc;
+        if (int rc = get_pack(c, idx, CRC_GPU_MAX_LOG2G, &pack)) return rc;
         a.pack = pack;
     }
     const mck_model_t &m = mck_models[idx];
@@ -1264,8 +1258,7 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
     if (fast) {
         // non-temporal loads for batches far past the Infinity Cache, sized
         // by count as for offsets batches (MCHECKSUM_GPU_NT=0/1 overrides)
-        const int nset = mck_settings()->gpu_nt;
-        const bool nt = nset >= 0 ? nset == 1 : count >= 8192;
+        const bool nt = nt_by_count(s, count);
         a.err_word = error_word();
         uint64_t blocks = (count + 15) / 16;
         if (blocks > (uint64_t)c->cus) blocks = (uint64_t)c->cus;
@@ -1273,13 +1266,7 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
         a.queue = sr.q;
         auto k = width == 32 ? (nt ? xdr_fast_kernel<32, true> : xdr_fast_kernel<32, false>)
                              : (nt ? xdr_fast_kernel<64, true> : xdr_fast_kernel<64, false>);
-        const hipError_t e = launch_kernel(k, dim3((unsigned)blocks), dim3(1024), (hipStream_t)stream, sr.done, a);
-        if (e != hipSuccess) {
-            slot_unissue(c, sr);
-            return hip_err(e, "XDR kernel launch");
-        }
-        slot_issued(sr);
-        return MCHECKSUM_GPU_OK;
+        return launch_slot(c, sr, k, (unsigned)blocks, 1024, stream, a, "XDR kernel launch");
     }
     uint64_t blocks = (count + 3) / 4;
     if (blocks > (uint64_t)c->cus * 8) blocks = (uint64_t)c->cus * 8;

@@ -91,7 +91,14 @@ def main():
                 a.record(s_); f(); b.record(s_)
             torch.cuda.synchronize()
             dev_us = float(np.median([a.elapsed_time(b) for a, b in ev])) * 1e3
-            r = {"light": light, "messages": count, "bytes": count * length, "verify_messages_device_us": round(dev_us, 2)}
+            n = 200
+            t1 = time.perf_counter()
+            for _ in range(n):
+                f()
+            capi_us = (time.perf_counter() - t1) / n * 1e6  # host cost of the entry point
+            torch.cuda.synchronize()
+            r = {"light": light, "messages": count, "bytes": count * length, "verify_messages_device_us": round(dev_us, 2),
+                 "capi_issue_us": round(capi_us, 2)}
             print(json.dumps(r), flush=True)
             res.append(r)
     json.dump(res, open(os.path.join(ROOT, "gpurun_out", "latency.json"), "w"), indent=1)
