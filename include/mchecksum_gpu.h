@@ -101,6 +101,69 @@ MCHECKSUM_PUBLIC int
 mchecksum_gpu_checksum_offsets(const char *hash_method, const void *dev_base,
     const uint64_t *dev_offsets, size_t count, void *dev_out, void *stream);
 
+/* Streaming batch checksums: init / update / get over many device-resident
+ * streams at once, for objects that arrive in chunks (a pipelined bulk
+ * transfer, an object larger than its staging buffer) and are never resident
+ * in one piece.
+ *
+ *   state_init, then ANY sequence of update_offsets calls, then state_get
+ *     == mchecksum_get() after mchecksum_update() over the same bytes in the
+ *        same order, bit for bit, per stream i;
+ *   state_init followed directly by state_get yields the CRC of the empty
+ *   message.
+ *
+ * dev_state holds `count` elements of the method's size (uint32_t /
+ * uint64_t): the running registers in the kernels' internal form -- opaque;
+ * only these calls interpret them.  Every 32/64-bit catalogue method,
+ * MSB-first ones included; 16-bit methods return MCHECKSUM_GPU_EMETHOD.
+ * Error codes, the stream convention, the 2^31-payload cap, the empty-batch
+ * rules (count 0 needs no buffers) and MCHECKSUM_GPU_ENODEV are those of
+ * mchecksum_gpu_checksum_offsets; update_offsets launches the seeded twin of
+ * the kernel checksum_offsets picks for the same count, with the same
+ * work-queue rules.
+ *
+ * All four calls are asynchronous and stream-ordered: an update sees the
+ * state its predecessors on the stream left.  They are capture-safe after
+ * mchecksum_gpu_prepare() (which uploads the Z^n shift pack they use: nothing
+ * is uploaded inside a capture); a replayed update_offsets advances the state
+ * again on every replay.  One stream of states must not be updated by two
+ * calls running at once.
+ *
+ * Fail closed as the checksum calls: an update_offsets call in which a device
+ * wait gave up adds 1 to the error word (mchecksum_gpu_set_error_word) and to
+ * mchecksum_gpu_queue_faults(); after such a call the states it touched are
+ * unspecified (some advanced, some not) and must be initialised again. */
+
+/* dev_state[i] = the method's initial register, i < count. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_init(const char *hash_method, void *dev_state,
+    size_t count, void *stream);
+
+/* dev_state[i] <- dev_state[i] advanced over dev_base[dev_offsets[i],
+ * dev_offsets[i+1]) (the checksum_offsets layout and memory rules).  A
+ * zero-length chunk leaves dev_state[i] unchanged: that is how a stream with
+ * nothing new this round is expressed. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_update_offsets(const char *hash_method, const void *dev_base,
+    const uint64_t *dev_offsets, size_t count, void *dev_state, void *stream);
+
+/* dev_out[i] = what mchecksum_get() returns after all updates so far (host
+ * order, method size).  Does not modify the state: more updates may follow.
+ * dev_out may alias dev_state (the states then hold values, not registers). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_get(const char *hash_method, const void *dev_state,
+    size_t count, void *dev_out, void *stream);
+
+/* dev_out[i] = CRC(A_i || B_i) from dev_crc_a[i] = CRC(A_i), dev_crc_b[i] =
+ * CRC(B_i) -- finalized values as the checksum_* calls and state_get return
+ * them -- and dev_len_b[i] = the bytes of B_i (< 2^48).  For chunks that
+ * complete out of order: hash each on its own, join afterwards, left to
+ * right.  dev_out may alias dev_crc_a or dev_crc_b. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a,
+    const void *dev_crc_b, const uint64_t *dev_len_b, size_t count,
+    void *dev_out, void *stream);
+
 /* Batched verify of received payloads against expected values (e.g. the
  * payload hash carried in the 4-byte HG header, src/mercury_header.c:111-112,
  * after ntohl): dev_status[i] = 1 if CRC(payload i) != dev_expected[i] else 0,

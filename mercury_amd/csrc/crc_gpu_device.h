@@ -13,6 +13,7 @@
 
 #include "crc_gpu_layout.h"
 #include "crc_gpu_mask.h"
+#include "crc_gpu_seed.h"
 
 namespace {
 
@@ -112,7 +113,10 @@ struct BatchArgs {
     // could not hash every payload (fail-closed report for checksum modes)
     uint32_t *err_word;
     // split CRC-64 pieces (crc64_batch_kernel<..., SPLIT>): each payload is
-    // 2^split_log2 pieces of kSplitBytes, recombined with the Z^n shift pack
+    // 2^split_log2 pieces of kSplitBytes, recombined with the Z^n shift pack.
+    // Seeded offsets kernels (<..., SEED>, mchecksum_gpu_update_offsets): the
+    // same pack advances the running registers, which `out` then points to
+    // (read and written in place, one element per payload)
     const void *shift;
     uint32_t split_log2;
     // MSB-first model on a verify call: the kernel's value is the CRC
@@ -1228,8 +1232,15 @@ __device__ __forceinline__ void emit(const BatchArgs &a, uint64_t p, T v, uint32
 template <bool LIGHT>
 constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 
-template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false>
+// SEED (offsets batches, mchecksum_gpu_update_offsets): instead of storing
+// x ^ xorout, the lane that owns payload p advances the running register
+// state[p] (BatchArgs::out) over the payload: state[p] = x ^ Z^n(state[p] ^
+// init), crc_gpu_seed.h.  Only that lane reads or writes state[p]: no atomics,
+// no extra pass.  A compile-time variant, so the unseeded kernels are the
+// code they were.
+template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false, bool SEED = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
+    static_assert(!SEED || (MODE == kOffsets && !VERIFY && LOG2G == 6), "seeded updates: offsets checksums");
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
     const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -1284,7 +1295,12 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
             const uint64_t n = m1 - o;
             const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
                                                 : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
-            if (gl == 0) {
+            if constexpr (SEED) {
+                if (gl == 0) {
+                    uint32_t *st = reinterpret_cast<uint32_t *>(a.out) + p;
+                    *st = mck_seed32(reinterpret_cast<const crc32_shift_pack_t *>(a.shift), x, *st, init, n);
+                }
+            } else if (gl == 0) {
                 if (VERIFY && a.msg) {
                     const bool bad = short_msg || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
                     if (a.status) a.status[p] = bad ? 1 : 0;
@@ -1330,6 +1346,10 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
 
 // Z^n(x) from the base-16 digit tables; n and x are wave-uniform on the chunk
 // paths (mchecksum_gpu_ext.hip) and the split CRC-64 pieces below, so the table words come through the scalar cache.
+// Not so in the seeded offsets kernels and the combine kernel, which run
+// mck_zshift32/64 (crc_gpu_seed.h, the same loop bounded by the pack's digit
+// count) with a per-lane n: there the table words come through vector loads --
+// at most 12 digit steps per payload, on one lane.
 __device__ __forceinline__ uint32_t shift32(const crc32_shift_pack_t *sp, uint32_t x, uint64_t n) {
     for (int k = 0; n; k++, n >>= 4) {
         const uint32_t d = (uint32_t)(n & 15u);
@@ -1788,8 +1808,10 @@ __device__ __forceinline__ uint64_t payload64_g64(const uint8_t *lds, const crc6
 // Z^(bytes after piece q)(L_q), L_0 carrying the initial value; each piece
 // adds its term (and piece 0 the final XOR) to out[p] with a 64-bit atomic
 // XOR, into an output the host zeroed before the launch.
-template <int LOG2G, int MODE, bool VERIFY, bool NT, bool SPLIT = false>
+// SEED: as in crc32c_batch_kernel (offsets batches only).
+template <int LOG2G, int MODE, bool VERIFY, bool NT, bool SPLIT = false, bool SEED = false>
 __global__ __launch_bounds__(kBlk64<MODE * 16 + LOG2G>, kWpe64<MODE * 16 + LOG2G>) void crc64_batch_kernel(BatchArgs a) {
+    static_assert(!SEED || (MODE == kOffsets && !VERIFY && !SPLIT && LOG2G == 6), "seeded updates: offsets checksums");
     using S = Shape<64, MODE, false, LOG2G>;
     constexpr int kWPB = S::block / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds[S::lds64_bytes];
@@ -1840,7 +1862,14 @@ __global__ __launch_bounds__(kBlk64<MODE * 16 + LOG2G>, kWpe64<MODE * 16 + LOG2G
             const uint64_t n = a.offsets[p + 1] - o;
             const uint64_t x = n < (1ull << 31) ? payload64_g64<NT, false, S::ops_mode>(lds, pk, a.base + o, n, gl, lc)
                                                 : payload64_generic<LOG2G, NT, S::ops_mode>(lds, pk, a.base + o, n, gl, lc);
-            if (gl == 0) emit<uint64_t, VERIFY>(a, p, x ^ xorout, nbad);
+            if constexpr (SEED) {
+                if (gl == 0) {
+                    uint64_t *st = reinterpret_cast<uint64_t *>(a.out) + p;
+                    *st = mck_seed64(reinterpret_cast<const crc64_shift_pack_t *>(a.shift), x, *st, pk->init, n);
+                }
+            } else {
+                if (gl == 0) emit<uint64_t, VERIFY>(a, p, x ^ xorout, nbad);
+            }
         };
         if (for_each_unit<true>(&wgq, a.queue, units, wave, nw, one)) fail_closed<VERIFY>(a);
         if constexpr (VERIFY) add_mismatches(a.mismatches, nbad);

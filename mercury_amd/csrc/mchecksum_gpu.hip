@@ -95,16 +95,8 @@ int resolve_model(const char *method, Model *out) {
 // A reflected model as is; an MSB-first model as the reflected model of the
 // same polynomial over bit-reversed bytes, conjugated by R (crc_gpu_layout.h):
 // rinit / xorout reflected, then R-mapped.
-crc_rmodel_t gpu_rmodel(int idx) {
-    const mck_model_t &m = mck_models[idx];
-    crc_rmodel_t rm{};
-    rm.width = m.width;
-    rm.rpoly = mck_reflect(m.poly, m.width);
-    rm.msb = !m.reflected;
-    rm.rinit = rm.msb ? crc_rev_bytes(m.width, mck_reflect(m.init, m.width)) : mck_reflect(m.init, m.width);
-    rm.xorout = rm.msb ? crc_rev_bytes(m.width, mck_reflect(m.xorout, m.width)) : m.xorout;
-    return rm;
-}
+// (crc_gpu_seed.h has the construction, so the CPU tests build the same model)
+crc_rmodel_t gpu_rmodel(int idx) { return mck_gpu_rmodel(&mck_models[idx]); }
 
 __global__ __launch_bounds__(256) void bswap_kernel(void *out, uint64_t n, int width) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
@@ -339,15 +331,24 @@ struct KLaunch {
     int block, blocks_per_cu;
 };
 
-template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false, bool SPLIT = false>
+template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false, bool SPLIT = false,
+          bool SEED = false>
 KLaunch kernel_ptr() {
     using S = Shape<W, MODE, LIGHT, LOG2G>;
-    if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT>, S::block, S::blocks_per_cu};
-    else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT>, S::block, S::blocks_per_cu};
+    if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED>, S::block, S::blocks_per_cu};
+    else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED>, S::block, S::blocks_per_cu};
 }
 
+// seed: the seeded twin of the checksum kernel the plan picks (update_offsets)
 template <int W>
-KLaunch offsets_kernel(const LaunchPlan &p, bool verify) {
+KLaunch offsets_kernel(const LaunchPlan &p, bool verify, bool seed) {
+    if (seed) {
+        if constexpr (W == 32) {
+            if (p.light) return kernel_ptr<W, 6, kOffsets, false, false, true, false, true>();
+        }
+        return p.nt ? kernel_ptr<W, 6, kOffsets, false, true, false, false, true>()
+                    : kernel_ptr<W, 6, kOffsets, false, false, false, false, true>();
+    }
     if constexpr (W == 32) {
         if (p.light)
             return verify ? kernel_ptr<W, 6, kOffsets, true, false, true>() : kernel_ptr<W, 6, kOffsets, false, false, true>();
@@ -381,9 +382,11 @@ KLaunch fixed_kernel(const LaunchPlan &p) {
 }
 
 // The kernel a plan (launch_plan.h) launches; verify: it compares with the
-// expected values instead of storing its own.
-KLaunch kernel_for(const LaunchPlan &p, bool verify) {
-    if (p.mode == kOffsets) return p.width == 32 ? offsets_kernel<32>(p, verify) : offsets_kernel<64>(p, verify);
+// expected values instead of storing its own; seed (offsets plans): it
+// advances running registers instead.
+KLaunch kernel_for(const LaunchPlan &p, bool verify, bool seed = false) {
+    if (p.mode == kOffsets)
+        return p.width == 32 ? offsets_kernel<32>(p, verify, seed) : offsets_kernel<64>(p, verify, seed);
     if (p.split)
         return p.nt ? kernel_ptr<64, 6, kFixedAligned, false, true, false, true>()
                     : kernel_ptr<64, 6, kFixedAligned, false, false, false, true>();
@@ -392,7 +395,9 @@ KLaunch kernel_for(const LaunchPlan &p, bool verify) {
 
 int do_offsets(const char *method, const void *base, const uint64_t *offsets, size_t count, void *out,
                const void *expected, uint8_t *status, uint32_t *mism, void *stream, bool verify,
-               bool msg = false, size_t pay_off = 0, size_t hash_off = 0) {
+               bool msg = false, size_t pay_off = 0, size_t hash_off = 0, bool seed = false) {
+    // seed (update_offsets): `out` is the running-register array, advanced in
+    // place by the seeded twin of the kernel the same plan picks
     // an empty batch needs no buffers (not even the one-entry offsets table)
     if (count && (!base || !offsets || (!verify && !out) || (verify && !msg && !expected)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
@@ -408,6 +413,8 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
     if (rc) return rc;
     const LaunchPlan p = plan_offsets(*mck_settings(), c->cus, m.width, count);
     if ((rc = get_pack(c, m.idx, p.lg, &pack))) return rc;
+    const void *shift = nullptr;
+    if (seed && (rc = get_ext(c, m.idx, &shift))) return rc;
     if (count == 0) return MCHECKSUM_GPU_OK;
     if (msg && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
@@ -425,12 +432,52 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
     a.hash_off = (uint32_t)hash_off;
     a.err_word = t_err_word;
     a.bswap = verify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
-    const KLaunch k = kernel_for(p, verify);
+    a.shift = shift;
+    const KLaunch k = kernel_for(p, verify, seed);
     SlotRef sr;
     if (p.dyn) sr = queue_slot(c, stream);
     a.queue = sr.q;
     rc = launch_slot(c, sr, k.k, p.grid, k.block, stream, a, "kernel launch");
-    if (rc == MCHECKSUM_GPU_OK && m.msb && !verify) rc = swap_outputs(out, count, m.width, stream);
+    // (registers stay in the kernels' form: state_get swaps an MSB-first model's)
+    if (rc == MCHECKSUM_GPU_OK && m.msb && !verify && !seed) rc = swap_outputs(out, count, m.width, stream);
+    return rc;
+}
+
+// ---- streaming state: 256-thread element kernels (grid: elem_grid) ----
+template <typename T>
+__global__ __launch_bounds__(256) void state_init_kernel(T *st, uint64_t n, T init) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) st[i] = init;
+}
+
+// out may alias st: every element is read, then written, by one thread
+template <typename T>
+__global__ __launch_bounds__(256) void state_get_kernel(const T *st, T *out, uint64_t n, T xorout, int msb) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        if constexpr (sizeof(T) == 8) out[i] = mck_reg_to_crc64(st[i], xorout, msb);
+        else out[i] = mck_reg_to_crc32(st[i], xorout, msb);
+    }
+}
+
+// out may alias a or b, element for element
+template <typename T>
+__global__ __launch_bounds__(256) void combine_kernel(const T *a, const T *b, const uint64_t *len_b, T *out, uint64_t n,
+                                                      const void *shift, T init, T xorout, int msb) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        if constexpr (sizeof(T) == 8)
+            out[i] = mck_combine64(reinterpret_cast<const crc64_shift_pack_t *>(shift), a[i], b[i], len_b[i], init, xorout, msb);
+        else
+            out[i] = mck_combine32(reinterpret_cast<const crc32_shift_pack_t *>(shift), a[i], b[i], len_b[i], init, xorout, msb);
+    }
+}
+
+// Common front of the element calls: the count cap, the device, the model
+// (its kernels' form in *rm) and the device context.
+int state_call(const char *method, size_t count, Model *m, crc_rmodel_t *rm, DevCtx **c) {
+    if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    int rc = resolve_model(method, m);
+    if (!rc) rc = device_ctx(c);
+    if (!rc) *rm = gpu_rmodel(m->idx);
     return rc;
 }
 
@@ -559,6 +606,71 @@ int mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf, 
                                   uint32_t *dev_mismatches, void *stream) {
     return do_offsets(hash_method, dev_buf, dev_msg_offsets, count, nullptr, nullptr, dev_status, dev_mismatches,
                       stream, true, true, payload_offset, hash_offset);
+}
+
+int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {
+    if (count && !dev_state) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    Model m;
+    crc_rmodel_t rm;
+    DevCtx *c = nullptr;
+    if (int rc = state_call(hash_method, count, &m, &rm, &c)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    const dim3 grid(elem_grid(count)), block(256);
+    const hipError_t e =
+        m.width == 64 ? launch_kernel(state_init_kernel<uint64_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (uint64_t *)dev_state, (uint64_t)count, (uint64_t)rm.rinit)
+                      : launch_kernel(state_init_kernel<uint32_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (uint32_t *)dev_state, (uint64_t)count, (uint32_t)rm.rinit);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "state init");
+}
+
+int mchecksum_gpu_update_offsets(const char *hash_method, const void *dev_base, const uint64_t *dev_offsets,
+                                 size_t count, void *dev_state, void *stream) {
+    return do_offsets(hash_method, dev_base, dev_offsets, count, dev_state, nullptr, nullptr, nullptr, stream, false,
+                      false, 0, 0, true);
+}
+
+int mchecksum_gpu_state_get(const char *hash_method, const void *dev_state, size_t count, void *dev_out,
+                            void *stream) {
+    if (count && (!dev_state || !dev_out)) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    Model m;
+    crc_rmodel_t rm;
+    DevCtx *c = nullptr;
+    if (int rc = state_call(hash_method, count, &m, &rm, &c)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    const dim3 grid(elem_grid(count)), block(256);
+    const hipError_t e =
+        m.width == 64 ? launch_kernel(state_get_kernel<uint64_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint64_t *)dev_state, (uint64_t *)dev_out, (uint64_t)count,
+                                      (uint64_t)rm.xorout, rm.msb)
+                      : launch_kernel(state_get_kernel<uint32_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint32_t *)dev_state, (uint32_t *)dev_out, (uint64_t)count,
+                                      (uint32_t)rm.xorout, rm.msb);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "state get");
+}
+
+int mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a, const void *dev_crc_b,
+                          const uint64_t *dev_len_b, size_t count, void *dev_out, void *stream) {
+    if (count && (!dev_crc_a || !dev_crc_b || !dev_len_b || !dev_out))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    Model m;
+    crc_rmodel_t rm;
+    DevCtx *c = nullptr;
+    if (int rc = state_call(hash_method, count, &m, &rm, &c)) return rc;
+    const void *shift = nullptr;
+    if (int rc = get_ext(c, m.idx, &shift)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    const dim3 grid(elem_grid(count)), block(256);
+    const hipError_t e =
+        m.width == 64 ? launch_kernel(combine_kernel<uint64_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint64_t *)dev_crc_a, (const uint64_t *)dev_crc_b, dev_len_b,
+                                      (uint64_t *)dev_out, (uint64_t)count, shift, (uint64_t)rm.rinit,
+                                      (uint64_t)rm.xorout, rm.msb)
+                      : launch_kernel(combine_kernel<uint32_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint32_t *)dev_crc_a, (const uint32_t *)dev_crc_b, dev_len_b,
+                                      (uint32_t *)dev_out, (uint64_t)count, shift, (uint32_t)rm.rinit,
+                                      (uint32_t)rm.xorout, rm.msb);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "combine");
 }
 
 const char *mchecksum_gpu_last_error(void) { return t_err; }

@@ -180,6 +180,89 @@ def checksum_offsets(method: str, data: torch.Tensor, offsets: torch.Tensor, out
     return out
 
 
+def _check_state(t, method: str, count: int, name: str):
+    if (not isinstance(t, torch.Tensor) or t.numel() < count or t.dtype != out_dtype(method) or not t.is_cuda
+            or not t.is_contiguous()):
+        raise GpuChecksumError(f"{name} tensor has the wrong size, dtype or device, or is not contiguous")
+
+
+def state_init(method: str, count: int, device=None, stream=None) -> torch.Tensor:
+    """Running state of `count` streams (mchecksum_gpu_state_init): a device
+    tensor of the method's size, opaque -- feed it to update_offsets and read
+    it with state_get."""
+    if count < 0:
+        raise GpuChecksumError("count must not be negative")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise GpuChecksumError("device must be a cuda/hip device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    state = torch.empty(count, dtype=out_dtype(method), device=device)
+    with _on(state):
+        rc = _lib().mchecksum_gpu_state_init(method.encode(), state.data_ptr(), count, _stream_handle(stream, device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_init")
+    return state
+
+
+def update_offsets(method: str, data: torch.Tensor, offsets: torch.Tensor, state: torch.Tensor, stream=None,
+                   offsets_host=None) -> torch.Tensor:
+    """Advance state[i] over data[offsets[i] : offsets[i+1]] in place (an empty
+    chunk leaves it unchanged).  Returns state."""
+    _check_device_u8(data, "data")
+    _check_offsets(data, offsets, offsets_host)
+    count = offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("offsets needs at least one entry")
+    _check_state(state, method, count, "state")
+    _same_device(data, offsets=offsets, state=state)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_update_offsets(method.encode(), data.data_ptr(), offsets.data_ptr(), count,
+                                                 state.data_ptr(), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_update_offsets")
+    return state
+
+
+def state_get(method: str, state: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """The CRC of every stream's bytes so far (host-order values, as the
+    checksum_* calls return them).  The state is left as it is."""
+    count = state.numel() if isinstance(state, torch.Tensor) else 0
+    _check_state(state, method, count, "state")
+    if out is None:
+        out = torch.empty(count, dtype=out_dtype(method), device=state.device)
+    _check_state(out, method, count, "out")
+    _same_device(state, out=out)
+    with _on(state):
+        rc = _lib().mchecksum_gpu_state_get(method.encode(), state.data_ptr(), count, out.data_ptr(),
+                                            _stream_handle(stream, state.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_get")
+    return out
+
+
+def combine(method: str, crc_a: torch.Tensor, crc_b: torch.Tensor, len_b: torch.Tensor,
+            out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """CRC(A_i || B_i) from crc_a[i] = CRC(A_i), crc_b[i] = CRC(B_i) and
+    len_b[i] = the bytes of B_i (device int64).  out may be crc_a or crc_b."""
+    count = crc_a.numel() if isinstance(crc_a, torch.Tensor) else 0
+    _check_state(crc_a, method, count, "crc_a")
+    _check_state(crc_b, method, count, "crc_b")
+    if (not isinstance(len_b, torch.Tensor) or len_b.dtype != torch.int64 or not len_b.is_cuda
+            or not len_b.is_contiguous() or len_b.numel() < count):
+        raise GpuChecksumError("len_b must be a contiguous device int64 tensor of at least count elements")
+    if out is None:
+        out = torch.empty(count, dtype=out_dtype(method), device=crc_a.device)
+    _check_state(out, method, count, "out")
+    _same_device(crc_a, crc_b=crc_b, len_b=len_b, out=out)
+    with _on(crc_a):
+        rc = _lib().mchecksum_gpu_combine(method.encode(), crc_a.data_ptr(), crc_b.data_ptr(), len_b.data_ptr(), count,
+                                          out.data_ptr(), _stream_handle(stream, crc_a.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_combine")
+    return out
+
+
 def verify_offsets(method: str, data: torch.Tensor, offsets: torch.Tensor, expected: torch.Tensor,
                    stream=None, offsets_host=None):
     """Returns (status uint8 per payload: 1 = mismatch, mismatch count tensor)."""
