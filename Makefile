@@ -53,7 +53,7 @@ $(LIB): $(COBJS) $(GOBJS) $(STAMP) | $(LIBDIR)
 	ln -sf libmchecksum.so $(LIBDIR)/libmchecksum.so.2
 
 # Test-only build: the work queue gives up one wait per launch
-# (MCK_QFAULT_TEST, crc_gpu_device.h), loaded by tests/test_gpu_fail_closed.py
+# (MCK_QFAULT_TEST, crc_gpu_queue.h), loaded by tests/test_gpu_fail_closed.py
 # next to the product library to check that such a launch fails closed.
 $(BUILD)/qfault_gpu.o: $(CSRC)/mchecksum_gpu.hip $(wildcard $(CSRC)/*.h) include/mchecksum_gpu.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DMCK_QFAULT_TEST=1 $(INC) -c $< -o $@

@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
-#    define MCK_HD __host__ __device__ __forceinline__
+#    define MCK_HD __host__ __device__ inline __attribute__((always_inline))
 #else
 #    define MCK_HD static inline
 #endif

@@ -12,13 +12,14 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "crc_gpu_device.h"
+#include "crc_gpu_plan.h"
+#include "crc_gpu_shape.h"
 #include "mchecksum_models.h"
 
 namespace mck {
 
 // The work queue counts chunk ids and per-workgroup slots in 32 bits
-// (crc_gpu_device.h, WgQueue): 2^31 payloads per call keeps both in range.
+// (crc_gpu_queue.h, WgQueue): 2^31 payloads per call keeps both in range.
 constexpr uint64_t kMaxUnits = 1ull << 31;
 
 struct LaunchPlan {
@@ -120,7 +121,7 @@ inline bool use_split(const mck_settings_t &s, int width, int lg, bool aligned, 
     return shape && nt;
 }
 
-// Block size and workgroups per CU of a kernel (Shape<>, crc_gpu_device.h; it
+// Block size and workgroups per CU of a kernel (Shape<>, crc_gpu_shape.h; it
 // does not depend on the lane count).
 inline void plan_shape(LaunchPlan &p) {
     if (p.light) {
@@ -182,7 +183,7 @@ inline LaunchPlan plan_fixed(const mck_settings_t &s, int cus, int width, uintpt
         p.units = (uint64_t)count << p.split_log2;
         p.grid = plan_grid(p, cus);
         // With a slot and queue chunks of whole payloads the pieces combine in
-        // their workgroup (crc_gpu_device.h, split_lds).  Otherwise they XOR
+        // their workgroup (crc_gpu_crc64.h, split_lds).  Otherwise they XOR
         // their terms into out[], zeroed first.  MCHECKSUM_GPU_SPLIT_LDS=0:
         // always through the zeroed output (tests, A/B).
         p.split_lds_ok = s.gpu_split_lds != 0 && SplitPlan(count, p.split_log2, p.grid).whole();

@@ -26,7 +26,7 @@
 //  * Persistent grid: one 1024-thread workgroup per CU for CRC-32C (the
 //    replicated tables take 128 KiB of the 160 KiB LDS), two for CRC-64.  Waves
 //    take payloads from a device-side work queue (large aligned CRC-32C and
-//    all offsets batches) or by a static stride (crc_gpu_device.h, dyn_policy).
+//    all offsets batches) or by a static stride (crc_gpu_shape.h, dyn_policy).
 //    Batches <= 16 MiB take a light layout: unreplicated tables, 256-thread
 //    workgroups on every CU.
 //  * Host side: each entry point validates its arguments, resolves the method
@@ -237,7 +237,7 @@ SlotRef queue_slot(DevCtx *c, void *stream) {
     std::lock_guard<std::mutex> lk(c->pool_mu);
     // A captured launch replays with these arguments, possibly on two graph
     // execs at once: no slot can be exclusive to it, so it takes the static
-    // split (crc_gpu_device.h, "Exclusivity").
+    // split (crc_gpu_queue.h, "Exclusivity").
     if (st != hipStreamCaptureStatusNone) {
         c->n_noslot++;
         return r;

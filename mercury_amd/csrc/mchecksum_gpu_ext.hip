@@ -78,7 +78,7 @@ struct SegArgs {
     uint64_t map_cap;
     void *out;
     const void *pack, *shift;
-    // work-queue slot of the chunk passes (crc_gpu_device.h, WgQueue; nullptr:
+    // work-queue slot of the chunk passes (crc_gpu_queue.h, WgQueue; nullptr:
     // static split) and the caller's fail-closed word
     unsigned long long *queue;
     uint32_t *err_word;
@@ -231,7 +231,7 @@ __device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_
     bool ok = true;
     if (b > 0) {
         int64_t k = (int64_t)b - 1;  // window: blocks k, k - 1, ..., k - 63 (lane order)
-        Deadline dl;  // 1 s of real time (crc_gpu_device.h)
+        Deadline dl;  // 1 s of real time (crc_gpu_queue.h)
         for (;;) {
 #if MCK_QFAULT_TEST
             if (b == fault_block && g_mck_qfault_mode == 0u) {  // injected give-up (test builds, MCHECKSUM_GPU_QFAULT_SCAN)
@@ -541,7 +541,7 @@ struct ChunkWalk {
 // of three measured within noise, and so did a one-round locate of bench.py's
 // seg layout from the chunk index alone; the same layout with a constant
 // chunk length measured +1.6-2.5% -- the compile-time trip count gave the
-// payload loop whole-ring code (payload64_even, crc_gpu_device.h), now taken
+// payload loop whole-ring code (payload64_even, crc_gpu_crc64.h), now taken
 // for every chunk of whole rings (profiles/r04/ab_seg_locate_bound.log,
 // ab_seg_cheats.log, ab_seg_full.log, ab_seg_head.log, ab_seg_even.log).
 __device__ __forceinline__ void seg_locate(const SegArgs &a, uint64_t c, uint64_t nchunks, uint64_t *addr,
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
             if (nt) ring64_load<true>(ring, reinterpret_cast<const uint8_t *>(k.p), lane);
             else ring64_load<false>(ring, reinterpret_cast<const uint8_t *>(k.p), lane);
         };
-        UnitTaker<ChunkPlan> tk(&wgq, a.queue, nchunks, wave, nw, false, ChunkPlan(nchunks));
+        UnitTaker<ChunkPlan> tk(&wgq, a.queue, nchunks, wave, nw, false, ChunkPlan(nchunks, gridDim.x));
         Lane64 ln = lane64(lc);
         uint4 ring[kRing64];
         uint64_t c = 0;
@@ -782,7 +782,7 @@ __global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) {
         if (a.status) a.status[m] = bad ? 1 : 0;
         nbad += bad;
     }
-    add_mismatches(a.mism, nbad);  // once per workgroup (crc_gpu_device.h)
+    add_mismatches(a.mism, nbad);  // once per workgroup (crc_gpu_common.h)
 }
 
 // ------------------------------------------------------------------ XDR ----
@@ -813,7 +813,7 @@ __global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) {
 // tables: an opaque or raw field of >= kXdrFastMin bytes is hashed by the
 // payload step loop (coalesced 1 KiB steps, payload32_g64 / payload64_g64 in
 // RAW form: zero init, no finalisation) instead of 64 byte-serial lane
-// ranges, and messages come from the work queue (crc_gpu_device.h).  The
+// ranges, and messages come from the work queue (crc_gpu_queue.h).  The
 // step loop starts from the running register itself (it rides in the field's
 // first bytes, R(L, M) = R(0, M ^ L)), so such a field needs no Z^n shift:
 // an iovec message (hg_perf_proc_iovec, Testing/perf/hg/mercury_perf.c:897-923:

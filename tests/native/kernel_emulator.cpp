@@ -1,11 +1,13 @@
 // kernel_emulator.cpp -- TEST ONLY.  Scalar emulation of the lane-parallel
 // batch-CRC algorithm that mercury_amd/csrc/mchecksum_gpu.hip runs on CDNA4,
-// using the very same host-built table packs (crc_tables.c).  It validates the
+// using the very same host-built table packs (crc_tables.c), window geometry
+// (crc_gpu_window.h) and edge handling (crc_gpu_mask.h).  It validates the
 // algebra (window alignment, sub-stream folding, tree combine, tail undo,
 // init handling) on the CPU against the oracle; the GPU parity tests then
 // cover what is GPU-specific (LDS layout, v_perm addressing, shuffles).
 #include "../../mercury_amd/csrc/crc_gpu_layout.h"
 #include "../../mercury_amd/csrc/crc_gpu_mask.h"
+#include "../../mercury_amd/csrc/crc_gpu_window.h"
 #include "../../oracle/crc_oracle.h"
 
 #include <cstdio>
@@ -35,32 +37,55 @@ static T raw_word(const uint8_t *buf, int64_t nbuf, int64_t wa) {
     return w;
 }
 
-// End of the step grid: the payload's end rounded up to 16 B, or -- with
-// EMU_GRID_ALIGN=128, the one-payload-per-wave loops (G = 64) of round 3 --
-// to the 128-B line, so every step covers whole lines.
-static int64_t grid_end(int64_t end, int log2g) {
-    const char *e = getenv("EMU_GRID_ALIGN");
-    const int64_t al = log2g == 6 && e && atoi(e) == 128 ? 128 : 16;
-    return (end + al - 1) & ~(al - 1);
-}
+// The 16-byte pieces of payload buf[start, start + len) as the kernels' loops
+// walk them: the per-lane window of the generic loops (LaneWindow) or -- with
+// EMU_GRID_ALIGN=128, the one-payload-per-wave loops (G = 64) -- the 1 KiB
+// step grid that ends on a 128-B line (GridWindow).  Buffer offsets stand in
+// for addresses (the buffer counts as 16-B aligned).
+struct Pieces {
+    bool grid;
+    LaneWindow lane;
+    GridWindow g64;
+    Pieces(int64_t start, int64_t len, int wbytes, int log2g)
+        : lane((uint64_t)start, (uint64_t)len, wbytes, log2g), g64((uint64_t)start, (uint64_t)len, (uint32_t)wbytes) {
+        const char *e = getenv("EMU_GRID_ALIGN");
+        grid = log2g == 6 && e && atoi(e) == 128;
+    }
+    int64_t steps() const { return grid ? (int64_t)g64.K : lane.K; }
+    uint32_t pad() const { return grid ? g64.pad() : lane.pad(); }
+    // Lane l's piece of step k, as the kernel treats it: its buffer offset
+    // (*at; -1: not read, the registers stay zero), the payload-relative
+    // position of its first byte (*lo) and whether it skips the masking.
+    bool clean(int64_t k, int l, int64_t *at, int64_t *lo) const {
+        if (grid) {
+            const uint32_t pos = (uint32_t)k * 1024u + 16u * (uint32_t)l;
+            *at = k == 0 && 16u * (uint32_t)l < g64.lead ? -1 : (int64_t)(g64.origin + pos);
+            *lo = (int32_t)pos - (int32_t)g64.qs;
+            return !g64.edge((uint32_t)k);
+        }
+        const int64_t pc = lane.piece(k, 16 * (int64_t)l);
+        *at = pc >= 0 ? (int64_t)lane.a0 + pc : -1;
+        *lo = pc - lane.hs;
+        return lane.clean(pc);
+    }
+};
 
 // CRC of payload buf[start, start+len) as the kernel computes it.
 extern "C" uint32_t emu_crc32(const crc32_gpu_pack_t *pk, const uint8_t *buf, int64_t nbuf, int64_t start,
                               int64_t len) {
     const int log2g = (int)pk->log2g, G = 1 << log2g;
-    const int64_t step = 16LL * G;
-    int64_t a0 = start & ~15LL, a1 = grid_end(start + len, log2g), t = a1 - (start + len);
-    int64_t W = a1 - a0, K = (W + step - 1) / step, r0 = W - K * step;
-    int64_t hs = start - a0, he = start + len - a0;
+    const Pieces win(start, len, 4, log2g);
+    const int64_t K = win.steps(), t = win.pad();
     std::vector<uint32_t> S(4 * G, 0);
     for (int64_t k = 0; k < K; k++)
         for (int l = 0; l < G; l++) {
-            int64_t pc = r0 + k * step + 16 * l;
+            int64_t at, lo;
+            const bool clean = win.clean(k, l, &at, &lo);
             uint32_t w[4] = {0, 0, 0, 0};
-            if (pc >= 0)
-                for (int j = 0; j < 4; j++) w[j] = raw_word<uint32_t>(buf, nbuf, a0 + pc + 4 * j);
-            if (!mck_piece_clean(pc, hs, he, 4))
-                for (int j = 0; j < 4; j++) w[j] = mck_mask32(w[j], pc - hs + 4 * j, len, pk->init);
+            if (at >= 0)
+                for (int j = 0; j < 4; j++) w[j] = raw_word<uint32_t>(buf, nbuf, at + 4 * j);
+            if (!clean)
+                for (int j = 0; j < 4; j++) w[j] = mck_mask32(w[j], lo + 4 * j, len, pk->init);
             for (int j = 0; j < 4; j++) {
                 uint32_t x = S[4 * l + j] ^ w[j];
                 S[4 * l + j] = pk->main[0][x & 255] ^ pk->main[1][(x >> 8) & 255] ^ pk->main[2][(x >> 16) & 255] ^
@@ -110,19 +135,18 @@ extern "C" uint32_t emu_crc32(const crc32_gpu_pack_t *pk, const uint8_t *buf, in
 extern "C" uint64_t emu_crc64(const crc64_gpu_pack_t *pk, const uint8_t *buf, int64_t nbuf, int64_t start,
                               int64_t len) {
     const int log2g = (int)pk->log2g, G = 1 << log2g;
-    const int64_t step = 16LL * G;
-    int64_t a0 = start & ~15LL, a1 = grid_end(start + len, log2g), t = a1 - (start + len);
-    int64_t W = a1 - a0, K = (W + step - 1) / step, r0 = W - K * step;
-    int64_t hs = start - a0, he = start + len - a0;
+    const Pieces win(start, len, 8, log2g);
+    const int64_t K = win.steps(), t = win.pad();
     std::vector<uint64_t> S(2 * G, 0);
     for (int64_t k = 0; k < K; k++)
         for (int l = 0; l < G; l++) {
-            int64_t pc = r0 + k * step + 16 * l;
+            int64_t at, lo;
+            const bool clean = win.clean(k, l, &at, &lo);
             uint64_t w[2] = {0, 0};
-            if (pc >= 0)
-                for (int j = 0; j < 2; j++) w[j] = raw_word<uint64_t>(buf, nbuf, a0 + pc + 8 * j);
-            if (!mck_piece_clean(pc, hs, he, 8))
-                for (int j = 0; j < 2; j++) w[j] = mck_mask64(w[j], pc - hs + 8 * j, len, pk->init);
+            if (at >= 0)
+                for (int j = 0; j < 2; j++) w[j] = raw_word<uint64_t>(buf, nbuf, at + 8 * j);
+            if (!clean)
+                for (int j = 0; j < 2; j++) w[j] = mck_mask64(w[j], lo + 8 * j, len, pk->init);
             for (int j = 0; j < 2; j++) {
                 uint64_t x = S[2 * l + j] ^ w[j], r = 0, r6 = 0;
                 for (int p = 0; p < 8; p++)
@@ -240,6 +264,31 @@ int main() {
                     if (e != g) { fails++; if (fails < 10) printf("%s lg=%d len=%ld start=%ld %016lx vs %016lx\n", mm.name, lg, (long)len, (long)start, (unsigned long)g, (unsigned long)e); }
                 }
         }
+    }
+    // The 1 KiB step grid's wave-uniform rule (GridWindow): every step in
+    // [kc0, kc1) is clean in all 64 lanes, so skipping the masking there is
+    // right, and a lane that step 0 does not read lies wholly before the
+    // payload, so its zero registers are right.  (Masking a clean piece is a
+    // no-op, so the range need not be tight.)
+    {
+        std::vector<int64_t> starts, lens = {0, 1, 3, 4, 7, 8, 9, 15, 16, 17};
+        for (int64_t s = 0; s < 130; s += 7) starts.push_back(s);
+        starts.push_back(1023);
+        starts.push_back(4097);
+        for (int64_t m : {127, 128, 255, 256, 1024, 1151, 4096, 65536})
+            for (int64_t d : {-1, 0, 1}) lens.push_back(m + d);
+        for (int wb : {4, 8})
+            for (int64_t start : starts)
+                for (int64_t len : lens) {
+                    const GridWindow g((uint64_t)start, (uint64_t)len, (uint32_t)wb);
+                    int bad = g.kc1 > g.K || g.qe - g.qs != (uint32_t)len || g.pad() > 127;
+                    for (uint32_t k = g.kc0; k < g.kc1; k++)
+                        for (uint32_t l = 0; l < 64; l++)
+                            bad += !mck_piece_clean((int64_t)k * 1024 + 16 * l, g.qs, g.qe, wb);
+                    for (uint32_t l = 0; 16 * l < g.lead; l++) bad += 16 * l + 16 > g.qs;
+                    n++;
+                    if (bad) { fails++; if (fails < 10) printf("grid window wb=%d start=%ld len=%ld: %d bad pieces\n", wb, (long)start, (long)len, bad); }
+                }
     }
     printf("%d cases, %d failures\n", n, fails);
     return fails != 0;

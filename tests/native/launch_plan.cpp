@@ -3,10 +3,11 @@
 // was taken from the scattered decision functions this header replaced (a
 // differential sweep over ~800 000 shapes agreed with them in every field),
 // so an edit that moves a threshold, a lane count or a grid fails here, on the
-// CPU.  Built with hipcc for the host only.
+// CPU.  Plain C++: no HIP header.
 #include "launch_plan.h"
 
 #include <cstdio>
+#include <initializer_list>
 
 using namespace mck;
 

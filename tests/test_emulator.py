@@ -61,7 +61,7 @@ def test_emulated_kernel_equals_oracle(emu, oracle_mod, log2g):
 @pytest.mark.parametrize("log2g", [6])
 def test_emulated_128b_grid_equals_oracle(emu, oracle_mod, log2g, monkeypatch):
     """The one-payload-per-wave loops end their step grid on a 128-B line
-    (round 3, crc_gpu_device.h kGridAlign): up to 127 pad bytes, undone by the
+    (round 3, crc_gpu_window.h kGridAlign): up to 127 pad bytes, undone by the
     tail table and the butterfly operators.  Every start alignment and lengths
     around each multiple of 16 and 128."""
     monkeypatch.setenv("EMU_GRID_ALIGN", "128")

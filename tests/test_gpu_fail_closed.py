@@ -3,7 +3,7 @@
 build/libmchecksum_qfault.so is libmchecksum built with -DMCK_QFAULT_TEST=1:
 in every launch that takes the work queue, workgroup 3 gives up the first unit
 of its second chunk, exactly as a wave whose bounded wait timed out would
-(crc_gpu_device.h, for_each_unit).  Such a launch must never report unhashed
+(crc_gpu_queue.h, for_each_unit).  Such a launch must never report unhashed
 bytes as good -- the contract hg_get_struct relies on when it turns a failed
 check into HG_CHECKSUM_ERROR (/root/reference/src/mercury.c:565-573):
 
@@ -237,7 +237,7 @@ def test_segment_scan_lookback_fault(gpu, qlib, monkeypatch):
     assert qlib.mchecksum_gpu_queue_faults() - faults0 >= 1
 
 
-# Deadline waits (crc_gpu_device.h, Deadline): 1 s of the 100 MHz real-time
+# Deadline waits (crc_gpu_queue.h, Deadline): 1 s of the 100 MHz real-time
 # counter, and once one wait of a call has given up every other one gives up
 # at once (the abort flag; a segments call whose scan failed hashes nothing).
 # A call whose waits are never satisfied returns within about one deadline

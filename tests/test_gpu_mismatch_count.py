@@ -1,7 +1,7 @@
 """Mismatch counts of the verify entry points when MANY payloads fail.
 
 The kernels count mismatches per lane and add them to the caller's counter
-once per wave (crc_gpu_device.h, add_mismatches; one atomic per bad payload
+once per wave (crc_gpu_common.h, add_mismatches; one atomic per bad payload
 made a corrupted buffer ten times slower to verify than a good one), so the
 count must stay exact across lanes, waves and workgroups, on the light and the
 throughput layouts and through the work queue -- and equal the number of

@@ -211,7 +211,7 @@ def test_graph_slot_is_never_reused_by_eager_launches(gpu, oracle_mod, monkeypat
 
 def test_captured_launches_replayed_concurrently_stay_correct(gpu, oracle_mod, monkeypatch):
     """Graph-captured launches get no work-queue slot and take the static split
-    (crc_gpu_device.h, "Exclusivity"): two offsets graphs, a split CRC-64 graph
+    (crc_gpu_queue.h, "Exclusivity"): two offsets graphs, a split CRC-64 graph
     (pieces XORed into a zeroed output, MCHECKSUM_GPU_SPLIT=1) and a
     scatter-gather graph (chunks XORed into out[]) replayed at the same time on
     four streams, next to eager queue launches on a fifth, keep returning the

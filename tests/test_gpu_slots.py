@@ -1,6 +1,6 @@
 """Work-queue slot lifecycle (round 4: a pool of idle slots).
 
-A slot (crc_gpu_device.h: the work-queue counters of two banks) serves one
+A slot (crc_gpu_queue.h: the work-queue counters of two banks) serves one
 launch at a time (mchecksum_gpu.hip, queue_slot):
 
 * every eager queue launch takes an idle slot from the device's pool and holds

@@ -1,4 +1,4 @@
-"""Split CRC-64 (crc_gpu_device.h, crc64_batch_kernel<..., SPLIT>): large
+"""Split CRC-64 (crc_gpu_crc64.h, crc64_batch_kernel<..., SPLIT>): large
 aligned payloads run as 256 KiB pieces on the work queue.  When every queue
 chunk holds whole payloads (SplitPlan::whole) the pieces combine in their
 workgroup's LDS and the last one stores the CRC; otherwise -- graph captures,

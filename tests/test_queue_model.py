@@ -1,4 +1,4 @@
-"""CPU model of the batch kernels' work-queue protocol (crc_gpu_device.h:
+"""CPU model of the batch kernels' work-queue protocol (crc_gpu_queue.h:
 WgQueue, wg_fetch, wg_publish, for_each_unit), run under random interleavings
 of every wave's shared-memory steps.  Checks what the GPU relies on: every
 unit is processed exactly once, no wait can block forever, and every launch
@@ -15,14 +15,16 @@ one deadline, not one per wait.
 Each wave is a generator that yields at every access to shared state (LDS or
 the global slot), so a seeded scheduler explores many orders of the same
 steps the device code takes.  A launch without a slot (graph captures, the
-per-thread stream, streams past the table: crc_gpu_device.h "Exclusivity")
+per-thread stream, streams past the table: crc_gpu_queue.h "Exclusivity")
 takes the static split and never touches any slot; the fail-closed fault flag
-is modelled too.  Fetch triggers, chunk sizes (chunk_log2, the
-eighth-size tail chunks of ChunkPlan), the
-round-robin sub-queues, the LDS ring recycling and the bank zeroing mirror the
-device code one to one.
+is modelled too.  Fetch triggers, the round-robin sub-queues, the LDS ring
+recycling and the bank zeroing mirror the device code one to one; the chunk
+plan (chunk_plan: chunk sizes, the eighth-size tail chunks) is compared with
+crc_gpu_plan.h's ChunkPlan, compiled for the host, number by number.
 """
+import os
 import random
+import subprocess
 
 import pytest
 
@@ -35,6 +37,25 @@ def chunk_log2(n, grid, max_log2=5):
     while lg < max_log2 and (2 << lg) <= share:
         lg += 1
     return lg
+
+
+class chunk_plan:
+    """ChunkPlan (crc_gpu_plan.h): full chunks of 2^cl units, then about one
+    full chunk per workgroup of units in eighth chunks (kQTailShift = 3)."""
+
+    def __init__(self, n, grid):
+        self.cl = cl = chunk_log2(n, grid)
+        self.sl = sl = cl - 3 if cl >= 3 else cl
+        tail = grid << cl
+        self.nbig = (n - tail) >> cl if n > tail else 0
+        self.big_end = self.nbig << cl
+        self.nch = self.nbig + ((n - self.big_end + (1 << sl) - 1) >> sl)
+
+    def start(self, cid):
+        return cid << self.cl if cid < self.nbig else self.big_end + ((cid - self.nbig) << self.sl)
+
+    def size(self, cid):
+        return 1 << self.cl if cid < self.nbig else 1 << self.sl
 
 
 class Bank:
@@ -129,27 +150,15 @@ def run_launches(launches, seed, slot=None, max_steps=4_000_000, deadline=20_000
 
 def _launch(spec, bank, rnd, res, clock, deadline):
     n, grid, waves_per_wg, drop, stall = spec["n"], spec["grid"], spec["wpw"], spec.get("drop"), spec.get("stall")
-    cl = chunk_log2(n, grid)
+    plan = chunk_plan(n, grid)
+    cl, nch, start, size = plan.cl, plan.nch, plan.start, plan.size
     cu, lead = 1 << cl, max(1, (1 << cl) // 4) if (1 << cl) > 4 else 1
-    # ChunkPlan: full chunks, then about one full chunk per workgroup of units
-    # in eighth chunks (MCK_QTAIL_SHIFT = 3)
-    sl = cl - 3 if cl >= 3 else cl
-    tail = grid << cl
-    nbig = (n - tail) >> cl if n > tail else 0
-    big_end = nbig << cl
-    nch = nbig + ((n - big_end + (1 << sl) - 1) >> sl)
-
-    def start(cid):
-        return cid << cl if cid < nbig else big_end + ((cid - nbig) << sl)
-
-    def size(cid):
-        return 1 << cl if cid < nbig else 1 << sl
     done_units = res["units"]
     lds = [Lds() for _ in range(grid)]
     cur, other = bank if bank else (None, None)
 
     def wait(cond):
-        """A bounded wait (crc_gpu_device.h Deadline): True when cond() holds,
+        """A bounded wait (crc_gpu_queue.h Deadline): True when cond() holds,
         False once it gave up -- after `deadline` polls, or at the next poll
         once the launch's abort flag is up (every 16th poll reads it)."""
         polls = 0
@@ -166,7 +175,7 @@ def _launch(spec, bank, rnd, res, clock, deadline):
         home = b % QSUB
         d = L.drained
         while d < QSUB:
-            # crc_gpu_device.h MCK_STEAL_ROT: a workgroup's victims after its
+            # crc_gpu_queue.h, wg_fetch's steal order: a workgroup's victims after its
             # home are the other seven rotated by (b / QSUB) % 7
             k = home if d == 0 else (home + 1 + (d - 1 + (b // QSUB) % (QSUB - 1)) % (QSUB - 1)) % QSUB
             t = cur.sub[k]
@@ -272,6 +281,36 @@ def test_chunk_size_rule():
     assert 1 << chunk_log2(100, 256) == 1
 
 
+# (n, grid) of every launch the tests of this file run through the model
+MODEL_SHAPES = [(1, 1), (2, 3), (17, 1), (67, 2), (67, 5), (100, 3), (257, 8), (1000, 9), (4096, 1), (4096, 16),
+                (20000, 8), (5000, 4), (262144 // 64, 8), (700, 4), (500, 3), (2000, 4), (5000, 8), (300, 2), (900, 4),
+                (900, 6), (700, 5), (1300, 9), (40, 3), (3000, 3),
+                # _split_model: count << psl units
+                (64 << 2, 2), (200 << 2, 3), ((8192 // 16) << 2, 4), (300 << 1, 4), (128 << 2, 1), (40 << 2, 1)]
+
+
+def test_model_plan_equals_the_header(tmp_path):
+    """The model's chunk plan against crc_gpu_plan.h's ChunkPlan, which
+    tests/native/split_plan.cpp (host compiler) prints as "plan n grid cl sl
+    nbig big_end nch" for a fixed list: every (n, grid) this file's tests run,
+    the chunk-size rule's three shapes and a grid of unit counts x workgroups."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "split_plan")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(root, "include"),
+                    "-I" + os.path.join(root, "mercury_amd", "csrc"),
+                    os.path.join(root, "tests", "native", "split_plan.cpp"), "-o", exe], check=True, capture_output=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120, check=True).stdout
+    rows = [tuple(int(v) for v in line.split()[1:]) for line in out.splitlines() if line.startswith("plan ")]
+    seen = set()
+    for n, grid, cl, sl, nbig, big_end, nch in rows:
+        p = chunk_plan(n, grid)
+        assert (p.cl, p.sl, p.nbig, p.big_end, p.nch) == (cl, sl, nbig, big_end, nch), (n, grid)
+        seen.add((n, grid))
+    want = set(MODEL_SHAPES) | {(262144, 256), (8192, 512), (100, 256)}
+    want |= {(n, g) for g in (1, 3, 8, 64, 255, 256, 512) for n in (0, 1, 2, 5, 63, 100, 1000, 8192, 262144)}
+    assert want <= seen, sorted(want - seen)
+
+
 @pytest.mark.parametrize("n,grid", [(67, 2), (5000, 4), (262144 // 64, 8)])
 def test_sixteen_waves_per_workgroup(n, grid):
     units, slot = run_model(n, grid, 16, n + grid)
@@ -374,20 +413,10 @@ def _split_model(count, psl, grid, wpw, seed, max_steps=6_000_000, deadline=200_
     n = count << psl
     pieces = 1 << psl
     rnd = random.Random(seed)
-    cl = chunk_log2(n, grid)
+    plan = chunk_plan(n, grid)
+    cl, sl, nch, start, size = plan.cl, plan.sl, plan.nch, plan.start, plan.size
     cu, lead = 1 << cl, (1 << cl) // 4 if (1 << cl) > 4 else 1
-    sl = cl - 3 if cl >= 3 else cl
     assert (1 << psl) <= (1 << sl) and (1 << cl) // (1 << psl) <= ACC, "not a whole-payload plan"
-    tail = grid << cl
-    nbig = (n - tail) >> cl if n > tail else 0
-    big_end = nbig << cl
-    nch = nbig + ((n - big_end + (1 << sl) - 1) >> sl)
-
-    def start(cid):
-        return cid << cl if cid < nbig else big_end + ((cid - nbig) << sl)
-
-    def size(cid):
-        return 1 << cl if cid < nbig else 1 << sl
     bank = Bank()
     lds = [Lds() for _ in range(grid)]
     acc = [[dict(tag=0, cnt=0) for _ in range(NA * ACC)] for _ in range(grid)]
