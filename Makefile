@@ -25,7 +25,8 @@ QFAULTLIB := $(BUILD)/libmchecksum_qfault.so
 STAMP_SRCS := $(sort $(wildcard $(CSRC)/*.c $(CSRC)/*.h $(CSRC)/*.hip include/*.h))
 STAMP     := $(BUILD)/src_stamp.o
 
-all: $(LIB) $(BENCHLIB) oracle $(BUILD)/c1_bench $(QFAULTLIB) $(BUILD)/libcpu_batch.so $(BUILD)/hg_verify_consumer
+all: $(LIB) $(BENCHLIB) oracle $(BUILD)/c1_bench $(QFAULTLIB) $(BUILD)/libcpu_batch.so $(BUILD)/hg_verify_consumer \
+     $(BUILD)/hg_seal_consumer
 
 $(BUILD) $(LIBDIR):
 	mkdir -p $@
@@ -86,6 +87,14 @@ $(BUILD)/hg_verify_consumer: tests/native/hg_verify_consumer.c tests/native/hg_c
 	cmake -S tests/native/hg_consumer -B $(BUILD)/hg_consumer -Dmchecksum_DIR=$(CURDIR)/cmake > /dev/null
 	cmake --build $(BUILD)/hg_consumer > /dev/null
 	cp $(BUILD)/hg_consumer/hg_verify_consumer $@
+
+# The compiled sender (pack, seal, then the receiver's verify calls), run by
+# tests/test_gpu_sender_consumer.py: one plain compiler line against the tree.
+ROCM_PATH ?= /opt/rocm
+$(BUILD)/hg_seal_consumer: tests/native/hg_seal_consumer.c include/mchecksum.h include/mchecksum_gpu.h $(LIB) | $(BUILD)
+	$(CC) -O2 -std=c11 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I$(ROCM_PATH)/include $< -o $@ \
+	  -L$(LIBDIR) -lmchecksum -L$(ROCM_PATH)/lib -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,$(ROCM_PATH)/lib
 
 # CPU-only artefacts (no hipcc needed): streaming API for host tests.
 cpu: $(LIBDIR)/libmchecksum_cpu.so

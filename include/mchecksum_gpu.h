@@ -50,6 +50,18 @@
  * `count` to the mismatch counter of a verify call and marks every payload it
  * cannot vouch for with status 1, so unhashed bytes never read as verified.
  *
+ * Sender side: mchecksum_gpu_pack_messages copies device-resident payloads
+ * behind their message headers, hashes them in the same pass and stores each
+ * value network-order in the message's HG header slot (what HG_PROC_TYPE's
+ * memcpy + mchecksum_update and hg_set_struct do per field and per handle,
+ * src/mercury_proc.h:124-143,162-181, src/mercury.c:699-707);
+ * mchecksum_gpu_seal_messages hashes payloads already in place, and
+ * mchecksum_gpu_seal_core_headers stores the CRC-16 of the core headers.  They
+ * write only the bytes named at their declarations, fail closed as the verify
+ * calls do (status 1 on every message the launch cannot vouch for; the hash
+ * slots of such messages are unspecified) and are capture-safe after
+ * mchecksum_gpu_prepare(): a replay packs or seals the current contents again.
+ *
  * Settings: the MCHECKSUM_* environment variables (variants, log level, the
  * MCHECKSUM_GPU_* launch-policy overrides of the A/B tools) are read once,
  * at the library's first use, never on the call path.
@@ -192,6 +204,43 @@ mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf,
     size_t hash_offset, uint8_t *dev_status, uint32_t *dev_mismatches,
     void *stream);
 
+/* Sender side of mchecksum_gpu_verify_messages, in place: the same message
+ * table and argument rules (hash_offset + 4 <= payload_offset; crc32c only,
+ * and the method is checked before the device).  For message i the CRC of
+ * dev_buf[dev_msg_offsets[i] + payload_offset, dev_msg_offsets[i+1]) is stored
+ * big-endian in the 4 bytes at dev_msg_offsets[i] + hash_offset, as
+ * hg_set_struct stores it (src/mercury.c:699-707), and dev_status[i]
+ * (optional) = 0.  A message shorter than payload_offset gets status 1 and is
+ * not written.  No byte other than the 4 hash bytes of a sealed message is
+ * written.  The payloads are read as in verify_messages (readable to the next
+ * 16-byte boundary). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
+/* Pack, hash and seal in one pass over the payload bytes.  Payload i =
+ * dev_src[dev_src_offsets[i], dev_src_offsets[i+1]) (the checksum_offsets
+ * layout: any start byte, readable to the next 16-byte boundary) is copied to
+ * dev_buf[dev_msg_offsets[i] + payload_offset, dev_msg_offsets[i+1]), and its
+ * CRC-32C is stored big-endian at dev_msg_offsets[i] + hash_offset; both
+ * tables hold count + 1 entries.  Message i fits iff
+ *   dev_msg_offsets[i+1] - dev_msg_offsets[i]
+ *       == payload_offset + (dev_src_offsets[i+1] - dev_src_offsets[i]);
+ * one that does not gets dev_status[i] = 1 and is not touched, a packed one 0.
+ * The call writes exactly the payload bytes and the 4 hash bytes of each
+ * fitting message -- no other header byte (the caller fills those), no gap, no
+ * byte past dev_msg_offsets[count] -- so dev_buf needs no padding.  Payloads
+ * of any size (2 GiB and more included).  The source range and the
+ * destination range must not overlap: the library cannot check that (the
+ * tables are on the device), and an overlapping call copies and hashes
+ * unspecified bytes.  Argument rules of mchecksum_gpu_seal_messages. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_messages(const char *hash_method, const void *dev_src,
+    const uint64_t *dev_src_offsets, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
 /* Scatter-gather objects: object j is the
  * concatenation, in order, of segments [dev_obj_first[j], dev_obj_first[j+1])
  * of the segment list (dev_seg_addr[s], dev_seg_len[s]) -- the shape of a bulk
@@ -237,6 +286,18 @@ MCHECKSUM_PUBLIC int
 mchecksum_gpu_verify_core_headers(const char *hash_method, int kind,
     const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
     uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
+
+/* Sender side of mchecksum_gpu_verify_core_headers, with its argument rules
+ * (kind, a 16-bit hash_method): the CRC over the host-order field images is
+ * stored big-endian in the header's hash field (request: offset 12, response:
+ * offset 4), as hg_core_header_request_proc / _response_proc encode it;
+ * dev_status[i] (optional) = 0.  A message shorter than 16 bytes gets status 1
+ * and is not touched.  Only the 2 hash bytes of each sealed header are
+ * written. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_core_headers(const char *hash_method, int kind,
+    void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+    uint8_t *dev_status, void *stream);
 
 /* XDR-mode proc checksum.  In a Mercury built with
  * MERCURY_USE_XDR (HG_HAS_XDR) the serialized buffer holds XDR -- every

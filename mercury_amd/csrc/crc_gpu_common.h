@@ -19,6 +19,15 @@ __device__ __forceinline__ uint32_t load_be32(const uint8_t *q) {
     return (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | (uint32_t)q[3];
 }
 
+// ... and its store (hg_set_struct's, src/mercury.c:699-707): four byte
+// stores, since the slot sits at any byte address.
+__device__ __forceinline__ void store_be32(uint8_t *q, uint32_t v) {
+    q[0] = (uint8_t)(v >> 24);
+    q[1] = (uint8_t)(v >> 16);
+    q[2] = (uint8_t)(v >> 8);
+    q[3] = (uint8_t)v;
+}
+
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
 // Payload bytes are read exactly once.  Non-temporal loads keep a batch far

@@ -12,6 +12,7 @@
 #include "crc_gpu_common.h"
 #include "crc_gpu_layout.h"
 #include "crc_gpu_mask.h"
+#include "crc_gpu_pack_store.h"
 #include "crc_gpu_queue.h"
 #include "crc_gpu_seed.h"
 #include "crc_gpu_shape.h"
@@ -170,6 +171,24 @@ __device__ void fill_lds32(uint8_t *lds, const crc32_gpu_pack_t *pk, F &&issue =
     }
 }
 
+// The copying payload loops (COPY, mchecksum_gpu_pack_messages): the lane that
+// folds a piece stores the bytes crc_gpu_pack_store.h names at dst + their
+// payload position.  A whole piece is one 16-byte store through an align-1
+// type (source and destination residues differ in general; one
+// global_store_dwordx4), an edge piece goes byte by byte.
+typedef u32x4_t piece16_t __attribute__((aligned(1)));
+typedef __attribute__((address_space(1))) uint8_t *gwbyte_t;
+__device__ __forceinline__ void store_piece(gwbyte_t dst, const PieceStore &s, const uint4 &v) {
+    if (s.whole()) {
+        *(__attribute__((address_space(1))) piece16_t *)(dst + s.lo) = u32x4_t{v.x, v.y, v.z, v.w};
+    } else {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++)
+            if (b >= s.b0 && b < s.b1) dst[s.lo + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3u)));
+    }
+}
+
 // Ring slot j % kRing holds the piece of step j, loaded kRing steps ahead.
 //
 // Aligned fixed-size payload: base 16-B aligned, len = K * 16G, no masking,
@@ -242,11 +261,12 @@ __device__ __forceinline__ uint32_t payload32_aligned(TAB lds, const uint8_t *p,
 }
 
 // Any alignment, any length (0 included).  Per-lane window; the wave loops to
-// the largest step count of its groups.
-template <int LOG2G, bool NT, class TAB>
+// the largest step count of its groups.  COPY: the payload is also stored at
+// dst (crc_gpu_pack_store.h).
+template <int LOG2G, bool NT, class TAB, bool COPY = false>
 __device__ __forceinline__ uint32_t payload32_generic(TAB lds, const crc32_gpu_pack_t *pk,
                                                       const uint8_t *p, uint64_t len, uint32_t gl, uint32_t lc0,
-                                                      uint32_t lc1) {
+                                                      uint32_t lc1, uint8_t *dst = nullptr) {
     const uint32_t init = pk->init;
     const LaneWindow win(reinterpret_cast<uint64_t>(p), len, 4, LOG2G);
     const int64_t K = win.K, r0 = win.r0, step = win.step, hs = win.hs, he = win.he;
@@ -285,6 +305,7 @@ __device__ __forceinline__ uint32_t payload32_generic(TAB lds, const crc32_gpu_p
             const uint4 raw = ring[u];
             ring[u] = fetch(j + kRing);
             if (j < K) {
+                if constexpr (COPY) store_piece((gwbyte_t)dst, mck_lane_piece_store(win, j, win.piece(j, lane_off)), raw);
                 const uint4 w = prep(j, raw);
                 x0 = f32s(lds, x0 ^ w.x, lc0, lc1);
                 x1 = f32s(lds, x1 ^ w.y, lc0, lc1);
@@ -317,10 +338,13 @@ __device__ __forceinline__ uint32_t tail32(TAB lds, uint32_t t, uint32_t x) {
 // object, mchecksum_gpu_ext.hip); a non-zero `reg` continues a running
 // register (the XDR walker's fields) and needs len >= 4, since it rides in
 // the first four payload bytes (R(reg, M) = R(0, M ^ reg)).
-template <bool NT, class TAB, bool RAW = false>
+// COPY: the lane that folds a piece also stores it at dst + (the piece's
+// position in the payload), crc_gpu_pack_store.h: the payload is read once for
+// the copy and the CRC.  dst is wave-uniform, at any alignment.
+template <bool NT, class TAB, bool RAW = false, bool COPY = false>
 __device__ __forceinline__ uint32_t payload32_g64(TAB lds, const crc32_gpu_pack_t *pk, const uint8_t *p,
                                                   uint64_t len, uint32_t gl, uint32_t lc0, uint32_t lc1,
-                                                  uint32_t reg = 0u) {
+                                                  uint32_t reg = 0u, uint8_t *dst = nullptr) {
     const uint32_t init = RAW ? reg : pk->init;
     const GridWindow win(reinterpret_cast<uint64_t>(p), len, 4);
     const uint32_t K = win.K, lead = win.lead;  // the window starts `lead` bytes into step 0
@@ -331,7 +355,11 @@ __device__ __forceinline__ uint32_t payload32_g64(TAB lds, const crc32_gpu_pack_
     constexpr uint32_t R = kRingOff;
 
     uint32_t x0 = 0, x1 = 0, x2 = 0, x3 = 0;
+    [[maybe_unused]] gwbyte_t db = nullptr;
+    if constexpr (COPY) db = (gwbyte_t)uniform64(reinterpret_cast<uint64_t>(dst));
     auto fold = [&](uint32_t kk, uint4 v) {
+        // (the raw piece: the masking below XORs the initial register into it)
+        if constexpr (COPY) store_piece(db, mck_grid_piece_store(win, kk, gl), v);
         if (kk < kc0 || kk >= kc1) {  // wave-uniform: an edge step
             const int32_t lo = (int32_t)(kk * 1024u + lo_lane) - (int32_t)qs;
             v.x = mck_mask32(v.x, lo, ilen, init);
@@ -384,9 +412,23 @@ constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 // init), crc_gpu_seed.h.  Only that lane reads or writes state[p]: no atomics,
 // no extra pass.  A compile-time variant, so the unseeded kernels are the
 // code they were.
-template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false, bool SEED = false>
+//
+// SEAL (message mode, mchecksum_gpu_seal_messages): the mirror of the message
+// verify -- the owning lane stores x ^ xorout big-endian in the message's hash
+// slot (BatchArgs::out = the writable view of base) instead of comparing it,
+// and status[p] = 1 only for a message shorter than its headers, which is not
+// written.
+// COPY (with SEAL, mchecksum_gpu_pack_messages): payload p comes from the
+// source table (base, offsets) and is also stored behind the headers of
+// message p of the destination (out, with its message table in `expected`),
+// by the payload loop itself; a message that does not fit -- its size is not
+// pay_off + the payload's -- gets status 1 and no byte written.
+template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false, bool SEED = false, bool SEAL = false,
+          bool COPY = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
     static_assert(!SEED || (MODE == kOffsets && !VERIFY && LOG2G == 6), "seeded updates: offsets checksums");
+    static_assert(!SEAL || (MODE == kOffsets && !VERIFY && !SEED && LOG2G == 6), "sealing: message-mode offsets");
+    static_assert(!COPY || SEAL, "packing seals what it copies");
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
     const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -435,6 +477,26 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     if (MODE == kOffsets) {
         auto one = [&](uint64_t p) {
             const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
+            if constexpr (COPY) {
+                const uint64_t *mo = reinterpret_cast<const uint64_t *>(a.expected);
+                const uint64_t d0 = mo[p], d1 = mo[p + 1];
+                // a payload that does not fit its message is hashed and copied as an empty one
+                const bool misfit = d1 - d0 != a.pay_off + (m1 - m0);
+                const uint64_t o = misfit ? m1 : m0, n = m1 - o;
+                uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + d0;
+                const uint32_t x =
+                    n < (1ull << 31)
+                        ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, msg + a.pay_off)
+                        : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, msg + a.pay_off);
+                if (gl == 0) {
+                    // (the hash slot's neighbours in its 16-byte granule are
+                    // other messages' payload and header bytes: byte stores
+                    // here, and whole-piece stores only inside a payload)
+                    if (!misfit) store_be32(msg + a.hash_off, x ^ xorout);
+                    if (a.status) a.status[p] = misfit ? 1 : 0;
+                }
+                return;
+            }
             // message mode: a message shorter than its headers fails verification
             const bool short_msg = a.msg && m1 - m0 < a.pay_off;
             const uint64_t o = a.msg ? (short_msg ? m1 : m0 + a.pay_off) : m0;
@@ -445,6 +507,18 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 if (gl == 0) {
                     uint32_t *st = reinterpret_cast<uint32_t *>(a.out) + p;
                     *st = mck_seed32(reinterpret_cast<const crc32_shift_pack_t *>(a.shift), x, *st, init, n);
+                }
+            } else if constexpr (SEAL) {
+                // In place.  The hash slot shares a 16-byte granule with the
+                // payload's first bytes (slot at 16..19, payload from 20), may
+                // share one with the previous message's tail, and lies in the
+                // pad bytes the previous message's last step reads: payload
+                // loads of this or another wave see its old or its new bytes.
+                // Those bytes are outside every payload, so mck_mask32 clears
+                // them before the fold and no value depends on which.
+                if (gl == 0) {
+                    if (!short_msg) store_be32(reinterpret_cast<uint8_t *>(a.out) + m0 + a.hash_off, x ^ xorout);
+                    if (a.status) a.status[p] = short_msg ? 1 : 0;
                 }
             } else if (gl == 0) {
                 if (VERIFY && a.msg) {
@@ -457,7 +531,8 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
             }
         };
         if constexpr (!LIGHT) {
-            if (for_each_unit<true>(&wgq, a.queue, units, wave, nw, one)) fail_closed<VERIFY>(a);
+            // (a sealing launch sweeps its statuses as a verify does, with no counter to add to)
+            if (for_each_unit<true>(&wgq, a.queue, units, wave, nw, one)) fail_closed<VERIFY || SEAL>(a);
         } else {  // static: a byte-balanced contiguous range per wave
             uint64_t first, last;
             wave_range(a.offsets, a.count, wave, nw, &first, &last);

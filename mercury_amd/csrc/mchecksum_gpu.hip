@@ -332,10 +332,11 @@ struct KLaunch {
 };
 
 template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false, bool SPLIT = false,
-          bool SEED = false>
+          bool SEED = false, bool SEAL = false, bool COPY = false>
 KLaunch kernel_ptr() {
     using S = Shape<W, MODE, LIGHT, LOG2G>;
-    if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED>, S::block, S::blocks_per_cu};
+    if constexpr (W == 32)
+        return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>, S::block, S::blocks_per_cu};
     else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED>, S::block, S::blocks_per_cu};
 }
 
@@ -355,6 +356,16 @@ KLaunch offsets_kernel(const LaunchPlan &p, bool verify, bool seed) {
     }
     if (verify) return p.nt ? kernel_ptr<W, 6, kOffsets, true, true>() : kernel_ptr<W, 6, kOffsets, true>();
     return p.nt ? kernel_ptr<W, 6, kOffsets, false, true>() : kernel_ptr<W, 6, kOffsets, false>();
+}
+
+// The sender twins of the CRC-32C message-mode kernel the plan picks (light,
+// full or NT): SEAL stores the hash in place, COPY also copies the payload.
+enum Sender : int { kNoSender = 0, kSeal = 1, kPack = 2 };
+template <bool COPY>
+KLaunch sender_kernel(const LaunchPlan &p) {
+    if (p.light) return kernel_ptr<32, 6, kOffsets, false, false, true, false, false, true, COPY>();
+    return p.nt ? kernel_ptr<32, 6, kOffsets, false, true, false, false, false, true, COPY>()
+                : kernel_ptr<32, 6, kOffsets, false, false, false, false, false, true, COPY>();
 }
 
 template <int W, int LOG2G>
@@ -383,8 +394,10 @@ KLaunch fixed_kernel(const LaunchPlan &p) {
 
 // The kernel a plan (launch_plan.h) launches; verify: it compares with the
 // expected values instead of storing its own; seed (offsets plans): it
-// advances running registers instead.
-KLaunch kernel_for(const LaunchPlan &p, bool verify, bool seed = false) {
+// advances running registers instead; sender (CRC-32C offsets plans): it seals
+// or packs messages.
+KLaunch kernel_for(const LaunchPlan &p, bool verify, bool seed = false, int sender = kNoSender) {
+    if (p.mode == kOffsets && sender != kNoSender) return sender == kPack ? sender_kernel<true>(p) : sender_kernel<false>(p);
     if (p.mode == kOffsets)
         return p.width == 32 ? offsets_kernel<32>(p, verify, seed) : offsets_kernel<64>(p, verify, seed);
     if (p.split)
@@ -441,6 +454,48 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
     // (registers stay in the kernels' form: state_get swaps an MSB-first model's)
     if (rc == MCHECKSUM_GPU_OK && m.msb && !verify && !seed) rc = swap_outputs(out, count, m.width, stream);
     return rc;
+}
+
+// seal_messages (src == nullptr: in place, the payloads are dev_buf's own) and
+// pack_messages (payload i = src[src_off[i], src_off[i+1]) goes behind the
+// headers of message i of dev_buf).  verify_messages' argument checks in its
+// order, with the method check ahead of the device's (an argument check, as in
+// verify_core_headers); then the same plan, queue rules and launch.
+int do_sender(const char *method, const void *src, const uint64_t *src_off, void *buf, const uint64_t *msg_off,
+              size_t count, size_t pay_off, size_t hash_off, uint8_t *status, void *stream, bool pack) {
+    if (count && (!buf || !msg_off || (pack && (!src || !src_off))))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (hash_off + 4 > pay_off || pay_off > (1u << 30))
+        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
+    if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
+    Model m;
+    int rc = resolve_model(method, &m);
+    if (rc) return rc;
+    if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    DevCtx *c = nullptr;
+    const void *tables = nullptr;
+    if ((rc = device_ctx(&c))) return rc;
+    const LaunchPlan p = plan_offsets(*mck_settings(), c->cus, m.width, count);
+    if ((rc = get_pack(c, m.idx, p.lg, &tables))) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    BatchArgs a{};
+    a.base = (const uint8_t *)(pack ? src : buf);
+    a.offsets = pack ? src_off : msg_off;
+    a.count = count;
+    a.out = buf;
+    a.expected = pack ? msg_off : nullptr;  // the COPY twin's destination message table
+    a.status = status;
+    a.pack = tables;
+    a.msg = 1u;
+    a.pay_off = (uint32_t)pay_off;
+    a.hash_off = (uint32_t)hash_off;
+    a.err_word = t_err_word;
+    const KLaunch k = kernel_for(p, false, false, pack ? kPack : kSeal);
+    SlotRef sr;
+    if (p.dyn) sr = queue_slot(c, stream);
+    a.queue = sr.q;
+    return launch_slot(c, sr, k.k, p.grid, k.block, stream, a, pack ? "pack kernel launch" : "seal kernel launch");
 }
 
 // ---- streaming state: 256-thread element kernels (grid: elem_grid) ----
@@ -606,6 +661,19 @@ int mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf, 
                                   uint32_t *dev_mismatches, void *stream) {
     return do_offsets(hash_method, dev_buf, dev_msg_offsets, count, nullptr, nullptr, dev_status, dev_mismatches,
                       stream, true, true, payload_offset, hash_offset);
+}
+
+int mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+                                size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
+    return do_sender(hash_method, nullptr, nullptr, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
+                     dev_status, stream, false);
+}
+
+int mchecksum_gpu_pack_messages(const char *hash_method, const void *dev_src, const uint64_t *dev_src_offsets,
+                                void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                size_t hash_offset, uint8_t *dev_status, void *stream) {
+    return do_sender(hash_method, dev_src, dev_src_offsets, dev_buf, dev_msg_offsets, count, payload_offset,
+                     hash_offset, dev_status, stream, true);
 }
 
 int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {

@@ -742,7 +742,13 @@ struct HdrArgs {
     uint32_t kind, reflected, init, xorout;
 };
 
-__global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) {
+// One body for the receiver's check and the sender's seal (SEAL: the value is
+// stored big-endian in the header's hash field instead of compared with it --
+// two byte stores, a message starts at any byte -- and a message shorter than
+// a header is not written; status 1).  No wait on the device in either, so
+// nothing to fail closed on.
+template <bool SEAL>
+__device__ __forceinline__ void core_header_body(const HdrArgs &a) {
     __shared__ uint16_t T[256];
     T[threadIdx.x] = a.table[threadIdx.x];
     __syncthreads();
@@ -762,14 +768,14 @@ __global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) {
             for (int b = 0; b < 8; b++) img[2 + b] = h[9 - b];  // big-endian on the wire, host LE image
             img[10] = h[10];
             img[11] = h[11];
-            wire = (uint32_t)h[12] << 8 | h[13];
+            if constexpr (!SEAL) wire = (uint32_t)h[12] << 8 | h[13];
             n = 12;
         } else {
             img[0] = h[0];
             img[1] = h[1];
             img[2] = h[3];
             img[3] = h[2];
-            wire = (uint32_t)h[4] << 8 | h[5];
+            if constexpr (!SEAL) wire = (uint32_t)h[4] << 8 | h[5];
             n = 4;
         }
         uint32_t r = a.init;
@@ -778,12 +784,24 @@ __global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) {
         } else {
             for (uint32_t i = 0; i < n; i++) r = ((r << 8) ^ T[((r >> 8) ^ img[i]) & 0xFFu]) & 0xFFFFu;
         }
-        const bool bad = !whole || ((r ^ a.xorout) & 0xFFFFu) != wire;
-        if (a.status) a.status[m] = bad ? 1 : 0;
-        nbad += bad;
+        if constexpr (SEAL) {
+            if (whole) {
+                uint8_t *q = const_cast<uint8_t *>(h) + (a.kind == MCHECKSUM_GPU_CORE_HEADER_REQUEST ? 12 : 4);
+                q[0] = (uint8_t)((r ^ a.xorout) >> 8);
+                q[1] = (uint8_t)(r ^ a.xorout);
+            }
+            if (a.status) a.status[m] = whole ? 0 : 1;
+        } else {
+            const bool bad = !whole || ((r ^ a.xorout) & 0xFFFFu) != wire;
+            if (a.status) a.status[m] = bad ? 1 : 0;
+            nbad += bad;
+        }
     }
-    add_mismatches(a.mism, nbad);  // once per workgroup (crc_gpu_common.h)
+    if constexpr (!SEAL) add_mismatches(a.mism, nbad);  // once per workgroup (crc_gpu_common.h)
 }
+
+__global__ __launch_bounds__(256) void core_header_kernel(HdrArgs a) { core_header_body<false>(a); }
+__global__ __launch_bounds__(256) void core_header_seal_kernel(HdrArgs a) { core_header_body<true>(a); }
 
 // ------------------------------------------------------------------ XDR ----
 //
@@ -1170,9 +1188,10 @@ int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev
     return rc;
 }
 
-int mchecksum_gpu_verify_core_headers(const char *hash_method, int kind, const void *dev_buf,
-                                      const uint64_t *dev_msg_offsets, size_t count, uint8_t *dev_status,
-                                      uint32_t *dev_mismatches, void *stream) {
+// verify_core_headers and seal_core_headers: the argument checks, the 16-bit
+// model's table and the launch.
+static int core_headers_call(const char *hash_method, int kind, const void *dev_buf, const uint64_t *dev_msg_offsets,
+                             size_t count, uint8_t *dev_status, uint32_t *dev_mismatches, void *stream, bool seal) {
     if ((count && !dev_buf) || !dev_msg_offsets) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
         return set_err(MCHECKSUM_GPU_EINVAL, "unknown core header kind %d", kind);
@@ -1202,9 +1221,22 @@ int mchecksum_gpu_verify_core_headers(const char *hash_method, int kind, const v
     a.xorout = (uint32_t)m.xorout;
     uint64_t blocks = (count + 255) / 256;
     if (blocks > (uint64_t)c->cus * 8) blocks = (uint64_t)c->cus * 8;
-    const hipError_t e = launch_kernel(core_header_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, nullptr, a);
+    const hipError_t e = launch_kernel(seal ? core_header_seal_kernel : core_header_kernel, dim3((unsigned)blocks),
+                                       dim3(256), (hipStream_t)stream, nullptr, a);
     if (e != hipSuccess) return hip_err(e, "core header kernel launch");
     return MCHECKSUM_GPU_OK;
+}
+
+int mchecksum_gpu_verify_core_headers(const char *hash_method, int kind, const void *dev_buf,
+                                      const uint64_t *dev_msg_offsets, size_t count, uint8_t *dev_status,
+                                      uint32_t *dev_mismatches, void *stream) {
+    return core_headers_call(hash_method, kind, dev_buf, dev_msg_offsets, count, dev_status, dev_mismatches, stream,
+                             false);
+}
+
+int mchecksum_gpu_seal_core_headers(const char *hash_method, int kind, void *dev_buf, const uint64_t *dev_msg_offsets,
+                                    size_t count, uint8_t *dev_status, void *stream) {
+    return core_headers_call(hash_method, kind, dev_buf, dev_msg_offsets, count, dev_status, nullptr, stream, true);
 }
 
 int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,

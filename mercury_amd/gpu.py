@@ -311,6 +311,78 @@ def verify_messages(data: torch.Tensor, msg_offsets: torch.Tensor, payload_offse
     return status, mism
 
 
+def _sender_status(data: torch.Tensor, count: int, status):
+    """Status of a sealing call: starts "not sealed", only a sealed message's
+    verdict overwrites it."""
+    if status is None:
+        return torch.ones(max(count, 0), dtype=torch.uint8, device=data.device)
+    if (not isinstance(status, torch.Tensor) or status.dtype != torch.uint8 or status.numel() < count
+            or not status.is_cuda or not status.is_contiguous()):
+        raise GpuChecksumError("status must be a contiguous device uint8 tensor of at least count elements")
+    return status
+
+
+def seal_messages(data: torch.Tensor, msg_offsets: torch.Tensor, payload_offset: int = 20, hash_offset: int = 16,
+                  method: str = "crc32c", stream=None, offsets_host=None, status=None) -> torch.Tensor:
+    """Sender side of verify_messages, in place: store the CRC of each message's
+    payload (from payload_offset on) network-order at hash_offset.  Returns
+    status (uint8 per message: 1 = shorter than payload_offset, not written).
+    Only the 4 hash bytes of each sealed message are written.  Pass a
+    preallocated `status` (uint8, >= count, filled with ones) to reuse it."""
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    status = _sender_status(data, count, status)
+    _same_device(data, msg_offsets=msg_offsets, status=status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_seal_messages(method.encode(), data.data_ptr(), msg_offsets.data_ptr(), count,
+                                                payload_offset, hash_offset, status.data_ptr(),
+                                                _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_messages")
+    return status
+
+
+def pack_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: torch.Tensor, msg_offsets: torch.Tensor,
+                  payload_offset: int = 20, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                  src_offsets_host=None, offsets_host=None, status=None) -> torch.Tensor:
+    """Pack, hash and seal in one pass: payload i = src[src_offsets[i] :
+    src_offsets[i+1]] is copied behind the headers of message i of `data`
+    (data[msg_offsets[i] + payload_offset : msg_offsets[i+1]]) and its CRC
+    stored network-order at msg_offsets[i] + hash_offset.  Returns status
+    (uint8 per message: 1 = the payload does not fit its message exactly, not
+    written).  Only payload and hash bytes are written; the caller fills the
+    other header bytes.  `src` and `data` must not overlap; with both host
+    tables given, the fit rule and the overlap of the two ranges are checked
+    here, otherwise the tables are trusted as in the C ABI."""
+    _check_device_u8(src, "src")
+    _check_device_u8(data, "data")
+    _check_offsets(src, src_offsets, src_offsets_host)
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0 or src_offsets.numel() != count + 1:
+        raise GpuChecksumError("src_offsets and msg_offsets need the same number (>= 1) of entries")
+    if src_offsets_host is not None and offsets_host is not None and count:
+        import numpy as np
+        so, mo = np.asarray(src_offsets_host, dtype=np.uint64), np.asarray(offsets_host, dtype=np.uint64)
+        if np.any(mo[1:] - mo[:-1] != so[1:] - so[:-1] + np.uint64(payload_offset)):
+            raise GpuChecksumError("a payload does not fit its message: message size != payload_offset + payload size")
+        s0, d0 = src.data_ptr() + int(so[0]), data.data_ptr() + int(mo[0])
+        if s0 < d0 + int(mo[-1] - mo[0]) and d0 < s0 + int(so[-1] - so[0]):
+            raise GpuChecksumError("the source and destination ranges overlap")
+    status = _sender_status(data, count, status)
+    _same_device(data, src=src, src_offsets=src_offsets, msg_offsets=msg_offsets, status=status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_pack_messages(method.encode(), src.data_ptr(), src_offsets.data_ptr(),
+                                                data.data_ptr(), msg_offsets.data_ptr(), count, payload_offset,
+                                                hash_offset, status.data_ptr(), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_messages")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its
@@ -462,6 +534,31 @@ def verify_core_headers(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str
     if rc != 0:
         _err(rc, "mchecksum_gpu_verify_core_headers")
     return status, mism
+
+
+def seal_core_headers(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str = "request",
+                      method: str = "crc16", stream=None, offsets_host=None, status=None) -> torch.Tensor:
+    """Sender side of verify_core_headers: store the CRC16 of each message's
+    16-byte Mercury core header (kind "request" or "response") big-endian in
+    its hash field.  Returns status (uint8 per message: 1 = shorter than a
+    header, not written)."""
+    from ._lib import CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE
+    k = {"request": CORE_HEADER_REQUEST, "response": CORE_HEADER_RESPONSE}.get(kind)
+    if k is None:
+        raise GpuChecksumError("kind must be 'request' or 'response'")
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    status = _sender_status(data, count, status)
+    _same_device(data, msg_offsets=msg_offsets, status=status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_seal_core_headers(method.encode(), k, data.data_ptr(), msg_offsets.data_ptr(),
+                                                    count, status.data_ptr(), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_core_headers")
+    return status
 
 
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
