@@ -26,7 +26,7 @@ STAMP_SRCS := $(sort $(wildcard $(CSRC)/*.c $(CSRC)/*.h $(CSRC)/*.hip include/*.
 STAMP     := $(BUILD)/src_stamp.o
 
 all: $(LIB) $(BENCHLIB) oracle $(BUILD)/c1_bench $(QFAULTLIB) $(BUILD)/libcpu_batch.so $(BUILD)/hg_verify_consumer \
-     $(BUILD)/hg_seal_consumer
+     $(BUILD)/hg_seal_consumer $(BUILD)/hg_unpack_consumer
 
 $(BUILD) $(LIBDIR):
 	mkdir -p $@
@@ -92,6 +92,13 @@ $(BUILD)/hg_verify_consumer: tests/native/hg_verify_consumer.c tests/native/hg_c
 # tests/test_gpu_sender_consumer.py: one plain compiler line against the tree.
 ROCM_PATH ?= /opt/rocm
 $(BUILD)/hg_seal_consumer: tests/native/hg_seal_consumer.c include/mchecksum.h include/mchecksum_gpu.h $(LIB) | $(BUILD)
+	$(CC) -O2 -std=c11 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I$(ROCM_PATH)/include $< -o $@ \
+	  -L$(LIBDIR) -lmchecksum -L$(ROCM_PATH)/lib -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,$(ROCM_PATH)/lib
+
+# The compiled receiver (pack, then unpack: bytes round-trip, one flipped bit
+# is found), run by tests/test_gpu_receiver_consumer.py.
+$(BUILD)/hg_unpack_consumer: tests/native/hg_unpack_consumer.c include/mchecksum.h include/mchecksum_gpu.h $(LIB) | $(BUILD)
 	$(CC) -O2 -std=c11 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I$(ROCM_PATH)/include $< -o $@ \
 	  -L$(LIBDIR) -lmchecksum -L$(ROCM_PATH)/lib -lamdhip64 \
 	  -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,$(ROCM_PATH)/lib

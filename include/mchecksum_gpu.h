@@ -62,6 +62,13 @@
  * slots of such messages are unspecified) and are capture-safe after
  * mchecksum_gpu_prepare(): a replay packs or seals the current contents again.
  *
+ * Receiver side: mchecksum_gpu_verify_messages checks received messages in
+ * place; mchecksum_gpu_unpack_messages also copies each payload out of the
+ * receive buffer to where it is consumed, in the same pass over its bytes
+ * (HG_PROC_TYPE on HG_DECODE copies each field out and feeds the same bytes to
+ * mchecksum_update, src/mercury_proc.h:124-143,162-181; hg_get_struct then
+ * compares, src/mercury.c:565-573).
+ *
  * Settings: the MCHECKSUM_* environment variables (variants, log level, the
  * MCHECKSUM_GPU_* launch-policy overrides of the A/B tools) are read once,
  * at the library's first use, never on the call path.
@@ -203,6 +210,43 @@ mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, uint8_t *dev_status, uint32_t *dev_mismatches,
     void *stream);
+
+/* Verify and copy out in one pass over the payload bytes: pack_messages'
+ * mirror on the receiver.  Message i = dev_buf[dev_msg_offsets[i],
+ * dev_msg_offsets[i+1]) with the table and memory rules of
+ * mchecksum_gpu_verify_messages (dev_buf readable to the next 16-byte
+ * boundary).  Its payload dev_buf[dev_msg_offsets[i] + payload_offset,
+ * dev_msg_offsets[i+1]) is copied to dev_dst[dev_dst_offsets[i],
+ * dev_dst_offsets[i+1]), its CRC-32C is computed in the same read and compared
+ * with the network-order u32 at dev_msg_offsets[i] + hash_offset; both tables
+ * hold count + 1 entries.  Message i fits iff
+ *   dev_msg_offsets[i+1] - dev_msg_offsets[i]
+ *       == payload_offset + (dev_dst_offsets[i+1] - dev_dst_offsets[i])
+ * (a message shorter than payload_offset never fits); one that does not gets
+ * dev_status[i] = 1, counts as one mismatch, and no destination byte of it is
+ * written.  A fitting message gets status 0 when its CRC matches, and status 1
+ * and one mismatch when it differs -- its destination then holds the payload
+ * bytes AS RECEIVED: the copy happens before the value is known, as Mercury
+ * has decoded by the time hg_get_struct compares.  Look at the status before
+ * the bytes.  The call writes exactly the destination bytes of fitting
+ * messages -- nothing before dev_dst_offsets[0], no gap between payloads,
+ * nothing past dev_dst_offsets[count] -- so dev_dst needs no padding; dev_buf
+ * is never written.  Payloads of any size (2 GiB and more included).  The
+ * destination range and dev_buf's range must not overlap: the library cannot
+ * check that (the tables are on the device), and an overlapping call copies
+ * and hashes unspecified bytes.  Either of dev_status and dev_mismatches may
+ * be NULL; *dev_mismatches is added to (the caller zeroes it).  Argument
+ * rules and their order are mchecksum_gpu_seal_messages' (layout, then the
+ * method -- crc32c only --, then the device); count == 0 needs no buffers.
+ * Plan, work-queue slot and capture rules of verify_messages: a replay
+ * unpacks the buffer's current contents.  Fails closed as the verify calls do
+ * (error word + 1, count added to *dev_mismatches, status 1 on every message
+ * the launch cannot vouch for, whose destination bytes are unspecified). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_messages(const char *hash_method, const void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+    uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
 
 /* Sender side of mchecksum_gpu_verify_messages, in place: the same message
  * table and argument rules (hash_offset + 4 <= payload_offset; crc32c only,

@@ -171,7 +171,8 @@ __device__ void fill_lds32(uint8_t *lds, const crc32_gpu_pack_t *pk, F &&issue =
     }
 }
 
-// The copying payload loops (COPY, mchecksum_gpu_pack_messages): the lane that
+// The copying payload loops (COPY, mchecksum_gpu_pack_messages and
+// mchecksum_gpu_unpack_messages): the lane that
 // folds a piece stores the bytes crc_gpu_pack_store.h names at dst + their
 // payload position.  A whole piece is one 16-byte store through an align-1
 // type (source and destination residues differ in general; one
@@ -423,12 +424,18 @@ constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 // message p of the destination (out, with its message table in `expected`),
 // by the payload loop itself; a message that does not fit -- its size is not
 // pay_off + the payload's -- gets status 1 and no byte written.
+// COPY (with VERIFY, mchecksum_gpu_unpack_messages): pack's mirror on the
+// receiver -- payload p of the message table (base, offsets) is also stored at
+// its place in the destination (out, with its table in `expected`), and the
+// owning lane's epilogue is the message verify's; a message whose size is not
+// pay_off + its destination's gets status 1, one mismatch and no byte written.
 template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false, bool SEED = false, bool SEAL = false,
           bool COPY = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
     static_assert(!SEED || (MODE == kOffsets && !VERIFY && LOG2G == 6), "seeded updates: offsets checksums");
     static_assert(!SEAL || (MODE == kOffsets && !VERIFY && !SEED && LOG2G == 6), "sealing: message-mode offsets");
-    static_assert(!COPY || SEAL, "packing seals what it copies");
+    static_assert(!COPY || SEAL || (VERIFY && MODE == kOffsets && !SEED && LOG2G == 6),
+                  "copying goes with sealing (pack) or with the message-mode verify (unpack)");
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
     const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -477,7 +484,26 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     if (MODE == kOffsets) {
         auto one = [&](uint64_t p) {
             const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
-            if constexpr (COPY) {
+            if constexpr (COPY && VERIFY) {
+                const uint64_t *dt = reinterpret_cast<const uint64_t *>(a.expected);
+                const uint64_t d0 = dt[p], d1 = dt[p + 1];
+                // a message that does not fit its destination (one shorter than its
+                // headers never does) is hashed and copied as an empty payload
+                const bool misfit = m1 - m0 != a.pay_off + (d1 - d0);
+                const uint64_t o = misfit ? m1 : m0 + a.pay_off, n = m1 - o;
+                uint8_t *dst = reinterpret_cast<uint8_t *>(a.out) + d0;
+                const uint32_t x =
+                    n < (1ull << 31)
+                        ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, dst)
+                        : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, dst);
+                if (gl == 0) {
+                    // (the bytes are stored as received: the value is known only after the copy)
+                    const bool bad = misfit || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
+                    if (a.status) a.status[p] = bad ? 1 : 0;
+                    nbad += bad;
+                }
+                return;
+            } else if constexpr (COPY) {
                 const uint64_t *mo = reinterpret_cast<const uint64_t *>(a.expected);
                 const uint64_t d0 = mo[p], d1 = mo[p + 1];
                 // a payload that does not fit its message is hashed and copied as an empty one

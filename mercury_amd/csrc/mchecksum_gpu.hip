@@ -360,12 +360,18 @@ KLaunch offsets_kernel(const LaunchPlan &p, bool verify, bool seed) {
 
 // The sender twins of the CRC-32C message-mode kernel the plan picks (light,
 // full or NT): SEAL stores the hash in place, COPY also copies the payload.
-enum Sender : int { kNoSender = 0, kSeal = 1, kPack = 2 };
+// kUnpack is the receiver's copying twin: VERIFY + COPY.
+enum Sender : int { kNoSender = 0, kSeal = 1, kPack = 2, kUnpack = 3 };
 template <bool COPY>
 KLaunch sender_kernel(const LaunchPlan &p) {
     if (p.light) return kernel_ptr<32, 6, kOffsets, false, false, true, false, false, true, COPY>();
     return p.nt ? kernel_ptr<32, 6, kOffsets, false, true, false, false, false, true, COPY>()
                 : kernel_ptr<32, 6, kOffsets, false, false, false, false, false, true, COPY>();
+}
+KLaunch unpack_kernel(const LaunchPlan &p) {
+    if (p.light) return kernel_ptr<32, 6, kOffsets, true, false, true, false, false, false, true>();
+    return p.nt ? kernel_ptr<32, 6, kOffsets, true, true, false, false, false, false, true>()
+                : kernel_ptr<32, 6, kOffsets, true, false, false, false, false, false, true>();
 }
 
 template <int W, int LOG2G>
@@ -394,9 +400,10 @@ KLaunch fixed_kernel(const LaunchPlan &p) {
 
 // The kernel a plan (launch_plan.h) launches; verify: it compares with the
 // expected values instead of storing its own; seed (offsets plans): it
-// advances running registers instead; sender (CRC-32C offsets plans): it seals
-// or packs messages.
+// advances running registers instead; sender (CRC-32C offsets plans): it seals,
+// packs or unpacks messages.
 KLaunch kernel_for(const LaunchPlan &p, bool verify, bool seed = false, int sender = kNoSender) {
+    if (p.mode == kOffsets && sender == kUnpack) return unpack_kernel(p);
     if (p.mode == kOffsets && sender != kNoSender) return sender == kPack ? sender_kernel<true>(p) : sender_kernel<false>(p);
     if (p.mode == kOffsets)
         return p.width == 32 ? offsets_kernel<32>(p, verify, seed) : offsets_kernel<64>(p, verify, seed);
@@ -456,13 +463,17 @@ int do_offsets(const char *method, const void *base, const uint64_t *offsets, si
     return rc;
 }
 
-// seal_messages (src == nullptr: in place, the payloads are dev_buf's own) and
+// seal_messages (src == nullptr: in place, the payloads are dev_buf's own),
 // pack_messages (payload i = src[src_off[i], src_off[i+1]) goes behind the
-// headers of message i of dev_buf).  verify_messages' argument checks in its
-// order, with the method check ahead of the device's (an argument check, as in
-// verify_core_headers); then the same plan, queue rules and launch.
+// headers of message i of dev_buf) and unpack_messages (pack's mirror: src is
+// the message buffer with its table, buf the destination with its table, and
+// the launch counts mismatches into mism).  verify_messages' argument checks
+// in its order, with the method check ahead of the device's (an argument
+// check, as in verify_core_headers); then the same plan, queue rules and launch.
 int do_sender(const char *method, const void *src, const uint64_t *src_off, void *buf, const uint64_t *msg_off,
-              size_t count, size_t pay_off, size_t hash_off, uint8_t *status, void *stream, bool pack) {
+              size_t count, size_t pay_off, size_t hash_off, uint8_t *status, void *stream, int kind,
+              uint32_t *mism = nullptr) {
+    const bool pack = kind != kSeal;  // two buffers, two tables
     if (count && (!buf || !msg_off || (pack && (!src || !src_off))))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (hash_off + 4 > pay_off || pay_off > (1u << 30))
@@ -484,18 +495,20 @@ int do_sender(const char *method, const void *src, const uint64_t *src_off, void
     a.offsets = pack ? src_off : msg_off;
     a.count = count;
     a.out = buf;
-    a.expected = pack ? msg_off : nullptr;  // the COPY twin's destination message table
+    a.expected = pack ? msg_off : nullptr;  // the COPY twins' destination table
     a.status = status;
+    a.mismatches = mism;
     a.pack = tables;
     a.msg = 1u;
     a.pay_off = (uint32_t)pay_off;
     a.hash_off = (uint32_t)hash_off;
     a.err_word = t_err_word;
-    const KLaunch k = kernel_for(p, false, false, pack ? kPack : kSeal);
+    const KLaunch k = kernel_for(p, kind == kUnpack, false, kind);
     SlotRef sr;
     if (p.dyn) sr = queue_slot(c, stream);
     a.queue = sr.q;
-    return launch_slot(c, sr, k.k, p.grid, k.block, stream, a, pack ? "pack kernel launch" : "seal kernel launch");
+    return launch_slot(c, sr, k.k, p.grid, k.block, stream, a,
+                       kind == kUnpack ? "unpack kernel launch" : pack ? "pack kernel launch" : "seal kernel launch");
 }
 
 // ---- streaming state: 256-thread element kernels (grid: elem_grid) ----
@@ -666,14 +679,22 @@ int mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf, 
 int mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
                                 size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
     return do_sender(hash_method, nullptr, nullptr, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
-                     dev_status, stream, false);
+                     dev_status, stream, kSeal);
 }
 
 int mchecksum_gpu_pack_messages(const char *hash_method, const void *dev_src, const uint64_t *dev_src_offsets,
                                 void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                 size_t hash_offset, uint8_t *dev_status, void *stream) {
     return do_sender(hash_method, dev_src, dev_src_offsets, dev_buf, dev_msg_offsets, count, payload_offset,
-                     hash_offset, dev_status, stream, true);
+                     hash_offset, dev_status, stream, kPack);
+}
+
+int mchecksum_gpu_unpack_messages(const char *hash_method, const void *dev_buf, const uint64_t *dev_msg_offsets,
+                                  size_t count, size_t payload_offset, size_t hash_offset, void *dev_dst,
+                                  const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_mismatches,
+                                  void *stream) {
+    return do_sender(hash_method, dev_buf, dev_msg_offsets, dev_dst, dev_dst_offsets, count, payload_offset,
+                     hash_offset, dev_status, stream, kUnpack, dev_mismatches);
 }
 
 int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {

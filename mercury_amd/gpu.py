@@ -311,6 +311,54 @@ def verify_messages(data: torch.Tensor, msg_offsets: torch.Tensor, payload_offse
     return status, mism
 
 
+def unpack_messages(data: torch.Tensor, msg_offsets: torch.Tensor, dst: torch.Tensor, dst_offsets: torch.Tensor,
+                    payload_offset: int = 20, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                    offsets_host=None, dst_offsets_host=None, status=None, mismatches=None):
+    """verify_messages that also copies the payloads out, in one pass: payload
+    i = data[msg_offsets[i] + payload_offset : msg_offsets[i+1]] goes to
+    dst[dst_offsets[i] : dst_offsets[i+1]] and its CRC is compared with the
+    network-order u32 at msg_offsets[i] + hash_offset.  Returns (status uint8
+    per message, count) with verify_messages' buffer-reuse rules.  Status 1 =
+    the CRC differs (the destination then holds the bytes as received) or the
+    message does not fit its destination exactly (nothing of it is written).
+    Only destination bytes of fitting messages are written.  `data` and `dst`
+    must not overlap; with both host tables given, the fit rule and the
+    overlap of the two ranges are checked here, otherwise the tables are
+    trusted as in the C ABI."""
+    _check_device_u8(data, "data")
+    _check_device_u8(dst, "dst")
+    _check_offsets(data, msg_offsets, offsets_host)
+    _check_offsets(dst, dst_offsets, dst_offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0 or dst_offsets.numel() != count + 1:
+        raise GpuChecksumError("msg_offsets and dst_offsets need the same number (>= 1) of entries")
+    if offsets_host is not None and dst_offsets_host is not None and count:
+        import numpy as np
+        mo, do = np.asarray(offsets_host, dtype=np.uint64), np.asarray(dst_offsets_host, dtype=np.uint64)
+        if np.any(mo[1:] - mo[:-1] != do[1:] - do[:-1] + np.uint64(payload_offset)):
+            raise GpuChecksumError("a message does not fit its destination: message size != payload_offset + "
+                                   "destination size")
+        s0, d0 = data.data_ptr() + int(mo[0]), dst.data_ptr() + int(do[0])
+        if s0 < d0 + int(do[-1] - do[0]) and d0 < s0 + int(mo[-1] - mo[0]):
+            raise GpuChecksumError("the message and destination ranges overlap")
+    if status is None:
+        status = torch.ones(max(count, 0), dtype=torch.uint8, device=data.device)
+    elif status.dtype != torch.uint8 or status.numel() < count or not status.is_cuda:
+        raise GpuChecksumError("status must be a device uint8 tensor of at least count elements")
+    mism = torch.zeros(1, dtype=torch.int32, device=data.device) if mismatches is None else mismatches
+    if mism.dtype != torch.int32 or not mism.is_cuda:
+        raise GpuChecksumError("mismatches must be a device int32 tensor")
+    _same_device(data, msg_offsets=msg_offsets, dst=dst, dst_offsets=dst_offsets, status=status, mismatches=mism)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_unpack_messages(method.encode(), data.data_ptr(), msg_offsets.data_ptr(), count,
+                                                  payload_offset, hash_offset, dst.data_ptr(), dst_offsets.data_ptr(),
+                                                  status.data_ptr(), mism.data_ptr(),
+                                                  _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_messages")
+    return status, mism
+
+
 def _sender_status(data: torch.Tensor, count: int, status):
     """Status of a sealing call: starts "not sealed", only a sealed message's
     verdict overwrites it."""
