@@ -17,6 +17,7 @@
 #include "crc_gpu_seed.h"
 #include "crc_gpu_shape.h"
 #include "crc_gpu_window.h"
+#include "launch_plan.h"
 
 namespace {
 
@@ -407,35 +408,17 @@ __device__ __forceinline__ uint32_t payload32_g64(TAB lds, const crc32_gpu_pack_
 template <bool LIGHT>
 constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 
-// SEED (offsets batches, mchecksum_gpu_update_offsets): instead of storing
-// x ^ xorout, the lane that owns payload p advances the running register
-// state[p] (BatchArgs::out) over the payload: state[p] = x ^ Z^n(state[p] ^
-// init), crc_gpu_seed.h.  Only that lane reads or writes state[p]: no atomics,
-// no extra pass.  A compile-time variant, so the unseeded kernels are the
-// code they were.
-//
-// SEAL (message mode, mchecksum_gpu_seal_messages): the mirror of the message
-// verify -- the owning lane stores x ^ xorout big-endian in the message's hash
-// slot (BatchArgs::out = the writable view of base) instead of comparing it,
-// and status[p] = 1 only for a message shorter than its headers, which is not
-// written.
-// COPY (with SEAL, mchecksum_gpu_pack_messages): payload p comes from the
-// source table (base, offsets) and is also stored behind the headers of
-// message p of the destination (out, with its message table in `expected`),
-// by the payload loop itself; a message that does not fit -- its size is not
-// pay_off + the payload's -- gets status 1 and no byte written.
-// COPY (with VERIFY, mchecksum_gpu_unpack_messages): pack's mirror on the
-// receiver -- payload p of the message table (base, offsets) is also stored at
-// its place in the destination (out, with its table in `expected`), and the
-// owning lane's epilogue is the message verify's; a message whose size is not
-// pay_off + its destination's gets status 1, one mismatch and no byte written.
-template <int LOG2G, int MODE, bool VERIFY, bool NT, bool LIGHT = false, bool SEED = false, bool SEAL = false,
-          bool COPY = false>
+// OP (launch_plan.h, BatchOp): what the owning lane does with a payload's CRC.
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(!SEED || (MODE == kOffsets && !VERIFY && LOG2G == 6), "seeded updates: offsets checksums");
-    static_assert(!SEAL || (MODE == kOffsets && !VERIFY && !SEED && LOG2G == 6), "sealing: message-mode offsets");
-    static_assert(!COPY || SEAL || (VERIFY && MODE == kOffsets && !SEED && LOG2G == 6),
-                  "copying goes with sealing (pack) or with the message-mode verify (unpack)");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false}), "no such batch kernel");
+    // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
+    enum : bool {
+        VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
+        SEED = OP == mck::kOpUpdate,
+        SEAL = OP == mck::kOpSeal || OP == mck::kOpPack,
+        COPY = OP == mck::kOpPack || OP == mck::kOpUnpack
+    };
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
     const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -485,8 +468,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
         auto one = [&](uint64_t p) {
             const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
             if constexpr (COPY && VERIFY) {
-                const uint64_t *dt = reinterpret_cast<const uint64_t *>(a.expected);
-                const uint64_t d0 = dt[p], d1 = dt[p + 1];
+                const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
                 // a message that does not fit its destination (one shorter than its
                 // headers never does) is hashed and copied as an empty payload
                 const bool misfit = m1 - m0 != a.pay_off + (d1 - d0);
@@ -504,8 +486,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 }
                 return;
             } else if constexpr (COPY) {
-                const uint64_t *mo = reinterpret_cast<const uint64_t *>(a.expected);
-                const uint64_t d0 = mo[p], d1 = mo[p + 1];
+                const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
                 // a payload that does not fit its message is hashed and copied as an empty one
                 const bool misfit = d1 - d0 != a.pay_off + (m1 - m0);
                 const uint64_t o = misfit ? m1 : m0, n = m1 - o;

@@ -17,6 +17,7 @@
 #include "crc_gpu_seed.h"
 #include "crc_gpu_shape.h"
 #include "crc_gpu_window.h"
+#include "launch_plan.h"
 
 namespace {
 
@@ -450,10 +451,11 @@ __device__ __forceinline__ uint64_t shift64(const crc64_shift_pack_t *sp, uint64
 // Z^(bytes after piece q)(L_q), L_0 carrying the initial value; each piece
 // adds its term (and piece 0 the final XOR) to out[p] with a 64-bit atomic
 // XOR, into an output the host zeroed before the launch.
-// SEED: as in crc32c_batch_kernel (offsets batches only).
-template <int LOG2G, int MODE, bool VERIFY, bool NT, bool SPLIT = false, bool SEED = false>
+// OP: as in crc32c_batch_kernel (checksum, verify and update only).
+template <int LOG2G, int MODE, int OP, bool NT, bool SPLIT = false>
 __global__ __launch_bounds__(kBlk64<MODE * 16 + LOG2G>, kWpe64<MODE * 16 + LOG2G>) void crc64_batch_kernel(BatchArgs a) {
-    static_assert(!SEED || (MODE == kOffsets && !VERIFY && !SPLIT && LOG2G == 6), "seeded updates: offsets checksums");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{64, LOG2G, MODE, OP, NT, false, SPLIT}), "no such batch kernel");
+    enum : bool { VERIFY = OP == mck::kOpVerify, SEED = OP == mck::kOpUpdate };  // (enumerators: see crc32c_batch_kernel)
     using S = Shape<64, MODE, false, LOG2G>;
     constexpr int kWPB = S::block / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds[S::lds64_bytes];
@@ -517,8 +519,7 @@ __global__ __launch_bounds__(kBlk64<MODE * 16 + LOG2G>, kWpe64<MODE * 16 + LOG2G
         if constexpr (VERIFY) add_mismatches(a.mismatches, nbad);
         return;
     }
-    if constexpr (SPLIT) {
-        static_assert(LOG2G == 6 && MODE == kFixedAligned && !VERIFY, "split pieces: aligned G = 64 checksums");
+    if constexpr (SPLIT) {  // (kernel_key_valid: aligned G = 64 checksums)
         const crc64_shift_pack_t *sp = reinterpret_cast<const crc64_shift_pack_t *>(a.shift);
         unsigned long long *out = reinterpret_cast<unsigned long long *>(a.out);
         // In-workgroup combine (split_lds, a slot launch whose queue chunks hold

@@ -98,7 +98,10 @@ struct BatchArgs {
     const uint64_t *offsets;
     uint64_t stride, len, count;
     void *out;
-    const void *expected;
+    union {
+        const void *expected;         // verify_offsets: the expected CRCs
+        const uint64_t *dst_offsets;  // pack and unpack: the table of the destination `out`
+    };
     uint8_t *status;
     uint32_t *mismatches;
     const void *pack;
@@ -113,7 +116,7 @@ struct BatchArgs {
     uint32_t *err_word;
     // split CRC-64 pieces (crc64_batch_kernel<..., SPLIT>): each payload is
     // 2^split_log2 pieces of kSplitBytes, recombined with the Z^n shift pack.
-    // Seeded offsets kernels (<..., SEED>, mchecksum_gpu_update_offsets): the
+    // Seeded offsets kernels (kOpUpdate, mchecksum_gpu_update_offsets): the
     // same pack advances the running registers, which `out` then points to
     // (read and written in place, one element per payload)
     const void *shift;

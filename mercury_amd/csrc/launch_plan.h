@@ -3,9 +3,9 @@
 // snapshot (the entry point reads mck_settings() once and passes it down, so
 // mchecksum_gpu_reload_settings() on another thread cannot change a launch
 // half way through its decisions).  No HIP runtime call, no global: the host
-// compiles and checks it on the CPU (tests/native/launch_plan.cpp); the
-// kernels themselves are looked up from a plan in mchecksum_gpu.hip
-// (kernel_for).
+// compiles and checks it on the CPU (tests/native/launch_plan.cpp), down to
+// the kernel a plan leads to for the call's operation (BatchOp, kernel_key);
+// mchecksum_gpu.hip only turns that key into a function pointer (kernel_for).
 #ifndef MCK_LAUNCH_PLAN_H
 #define MCK_LAUNCH_PLAN_H
 
@@ -218,6 +218,94 @@ inline LaunchPlan plan_offsets(const mck_settings_t &s, int cus, int width, size
     plan_shape(p);
     p.grid = plan_grid(p, cus);
     return p;
+}
+
+// What a batch call does with each payload's CRC x: the one name an entry
+// point gives its call, carried through the host front into the kernels'
+// template arguments.  The kernels derive their compile-time variants from it
+// (VERIFY = verify or unpack, SEED = update, SEAL = seal or pack, COPY = pack
+// or unpack), so a kernel without one of them is the code it was.
+enum BatchOp : int {
+    // out[p] = x ^ xorout.
+    kOpChecksum,
+    // Compares instead of storing: status[p], and the launch's count in
+    // *mismatches.  verify_offsets compares with expected[p]; verify_messages
+    // (BatchArgs::msg, a run-time field: the same kernels) with the big-endian
+    // hash in the message's header, and a message shorter than its headers fails.
+    kOpVerify,
+    // Offsets batches, mchecksum_gpu_update_offsets: instead of storing
+    // x ^ xorout, the lane that owns payload p advances the running register
+    // state[p] (BatchArgs::out) over the payload: state[p] = x ^ Z^n(state[p] ^
+    // init), crc_gpu_seed.h.  Only that lane reads or writes state[p]: no
+    // atomics, no extra pass.
+    kOpUpdate,
+    // Message mode, mchecksum_gpu_seal_messages: the mirror of the message
+    // verify -- the owning lane stores x ^ xorout big-endian in the message's
+    // hash slot (BatchArgs::out = the writable view of base) instead of
+    // comparing it, and status[p] = 1 only for a message shorter than its
+    // headers, which is not written.
+    kOpSeal,
+    // Seal and copy, mchecksum_gpu_pack_messages: payload p comes from the
+    // source table (base, offsets) and is also stored behind the headers of
+    // message p of the destination (out, with its message table in
+    // dst_offsets), by the payload loop itself; a message that does not fit --
+    // its size is not pay_off + the payload's -- gets status 1 and no byte
+    // written.
+    kOpPack,
+    // Verify and copy, mchecksum_gpu_unpack_messages: pack's mirror on the
+    // receiver -- payload p of the message table (base, offsets) is also stored
+    // at its place in the destination (out, with its table in dst_offsets), and
+    // the owning lane's epilogue is the message verify's; a message whose size
+    // is not pay_off + its destination's gets status 1, one mismatch and no
+    // byte written.
+    kOpUnpack,
+};
+
+// One instantiation of the batch kernels (crc32c_batch_kernel,
+// crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
+struct KernelKey {
+    int width, lg, mode, op;
+    bool nt, light, split;
+};
+constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
+    return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
+           a.split == b.split;
+}
+
+// The instantiations there are -- kernel_for has exactly these, and each
+// kernel asserts it is one of them.
+constexpr bool kernel_key_valid(const KernelKey &k) {
+    if ((k.width != 32 && k.width != 64) || k.lg < 0 || k.lg > CRC_GPU_MAX_LOG2G) return false;
+    if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
+    if (k.split)  // pieces of aligned CRC-64 payloads, 64 lanes each: checksums only
+        return k.width == 64 && k.mode == kFixedAligned && k.lg == CRC_GPU_MAX_LOG2G && k.op == kOpChecksum;
+    switch (k.mode) {
+        case kFixedAligned: return k.op == kOpChecksum;
+        case kFixedGeneric: return k.op == kOpChecksum && !k.nt;  // no non-temporal form
+        case kOffsets: break;
+        default: return false;
+    }
+    if (k.lg != CRC_GPU_MAX_LOG2G) return false;  // offsets batches: one payload per wave
+    switch (k.op) {
+        case kOpChecksum:
+        case kOpVerify:
+        case kOpUpdate: return true;
+        case kOpSeal:
+        case kOpPack:
+        case kOpUnpack: return k.width == 32;  // the HG header carries a 32-bit hash
+        default: return false;
+    }
+}
+
+// The kernel a plan launches for op.  A plan's fields say what the batch is
+// like; the key drops what the kernel in question has no form for.
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split};
+    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true};
+    if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
+    if (k.width != 32) k.light = false;
+    if (k.light || k.mode == kFixedGeneric) k.nt = false;
+    return k;
 }
 
 }  // namespace mck

@@ -32,9 +32,11 @@
 //  * Host side: each entry point validates its arguments, resolves the method
 //    once (resolve_model), takes the device context, decides the whole launch
 //    in one pure plan from one settings snapshot (launch_plan.h: plan_fixed,
-//    plan_offsets), fetches the table pack for the plan's lane count, looks
-//    the kernel up from the plan (kernel_for) and launches it with its
-//    work-queue slot, if the plan takes one (gpu_host.h: launch_slot).
+//    plan_offsets), fetches the table pack for the plan's lane count, names
+//    the kernel for the plan and the call's operation (launch_plan.h: BatchOp,
+//    kernel_key), looks it up (kernel_for) and launches it with its
+//    work-queue slot, if the plan takes one (gpu_host.h: launch_slot).  The
+//    offsets-shaped calls share one front, offsets_call.
 // No MFMA: this is HBM-bound byte scanning; the roofline is HBM read bandwidth.
 #include <hip/hip_runtime.h>
 
@@ -44,6 +46,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "crc_gpu_device.h"
 #include "gpu_host.h"
@@ -56,8 +59,10 @@ namespace mck {
 
 thread_local char t_err[256] = "";
 // mchecksum_gpu_set_error_word(): device word bumped by a launch that could
-// not hash every payload (per host thread; nullptr = none)
-thread_local uint32_t *t_err_word = nullptr;
+// not hash every payload (per host thread; nullptr = none).  Launches read it
+// through error_word().
+static thread_local uint32_t *t_err_word = nullptr;
+uint32_t *error_word() { return t_err_word; }
 
 int set_err(int rc, const char *fmt, ...) {
     va_list ap;
@@ -318,8 +323,6 @@ void slot_unissue(DevCtx *c, SlotRef &r) {
     r.st = nullptr;
 }
 
-uint32_t *error_word() { return t_err_word; }
-
 typedef void (*kern_t)(BatchArgs);
 
 __global__ __launch_bounds__(256) void zero_u64_kernel(unsigned long long *p, uint64_t n) {
@@ -327,188 +330,127 @@ __global__ __launch_bounds__(256) void zero_u64_kernel(unsigned long long *p, ui
 }
 
 struct KLaunch {
-    kern_t k;
-    int block, blocks_per_cu;
+    kern_t k = nullptr;
+    int block = 0, blocks_per_cu = 0;
 };
 
-template <int W, int LOG2G, int MODE, bool VERIFY, bool NT = false, bool LIGHT = false, bool SPLIT = false,
-          bool SEED = false, bool SEAL = false, bool COPY = false>
+// The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT>
 KLaunch kernel_ptr() {
-    using S = Shape<W, MODE, LIGHT, LOG2G>;
-    if constexpr (W == 32)
-        return {crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>, S::block, S::blocks_per_cu};
-    else return {crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED>, S::block, S::blocks_per_cu};
-}
-
-// seed: the seeded twin of the checksum kernel the plan picks (update_offsets)
-template <int W>
-KLaunch offsets_kernel(const LaunchPlan &p, bool verify, bool seed) {
-    if (seed) {
-        if constexpr (W == 32) {
-            if (p.light) return kernel_ptr<W, 6, kOffsets, false, false, true, false, true>();
-        }
-        return p.nt ? kernel_ptr<W, 6, kOffsets, false, true, false, false, true>()
-                    : kernel_ptr<W, 6, kOffsets, false, false, false, false, true>();
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT})) {
+        using S = Shape<W, MODE, LIGHT, LOG2G>;
+        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT>, S::block, S::blocks_per_cu};
+        else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
-    if constexpr (W == 32) {
-        if (p.light)
-            return verify ? kernel_ptr<W, 6, kOffsets, true, false, true>() : kernel_ptr<W, 6, kOffsets, false, false, true>();
-    }
-    if (verify) return p.nt ? kernel_ptr<W, 6, kOffsets, true, true>() : kernel_ptr<W, 6, kOffsets, true>();
-    return p.nt ? kernel_ptr<W, 6, kOffsets, false, true>() : kernel_ptr<W, 6, kOffsets, false>();
+    return {};
 }
 
-// The sender twins of the CRC-32C message-mode kernel the plan picks (light,
-// full or NT): SEAL stores the hash in place, COPY also copies the payload.
-// kUnpack is the receiver's copying twin: VERIFY + COPY.
-enum Sender : int { kNoSender = 0, kSeal = 1, kPack = 2, kUnpack = 3 };
-template <bool COPY>
-KLaunch sender_kernel(const LaunchPlan &p) {
-    if (p.light) return kernel_ptr<32, 6, kOffsets, false, false, true, false, false, true, COPY>();
-    return p.nt ? kernel_ptr<32, 6, kOffsets, false, true, false, false, false, true, COPY>()
-                : kernel_ptr<32, 6, kOffsets, false, false, false, false, false, true, COPY>();
-}
-KLaunch unpack_kernel(const LaunchPlan &p) {
-    if (p.light) return kernel_ptr<32, 6, kOffsets, true, false, true, false, false, false, true>();
-    return p.nt ? kernel_ptr<32, 6, kOffsets, true, true, false, false, false, false, true>()
-                : kernel_ptr<32, 6, kOffsets, true, false, false, false, false, false, true>();
+// f(std::integral_constant<int, x>) for a run-time x in [0, N); no kernel outside.
+template <int N, class F>
+KLaunch lift(int x, const F &f) {
+    if constexpr (N > 0) return x == N - 1 ? f(std::integral_constant<int, N - 1>{}) : lift<N - 1>(x, f);
+    return {};
 }
 
-template <int W, int LOG2G>
-KLaunch fixed_kernel_lg(const LaunchPlan &p) {
-    if constexpr (W == 32) {
-        if (p.light)
-            return p.aligned ? kernel_ptr<W, LOG2G, kFixedAligned, false, false, true>()
-                             : kernel_ptr<W, LOG2G, kFixedGeneric, false, false, true>();
-    }
-    if (!p.aligned) return kernel_ptr<W, LOG2G, kFixedGeneric, false>();
-    return p.nt ? kernel_ptr<W, LOG2G, kFixedAligned, false, true>() : kernel_ptr<W, LOG2G, kFixedAligned, false>();
+// The kernel of a key (launch_plan.h: kernel_key): each field becomes a
+// template argument in turn.  A key with no kernel gives a null KLaunch, which
+// the callers report as an error and never launch.
+KLaunch kernel_for(const KernelKey &k) {
+    return lift<2>(k.width == 32 ? 0 : k.width == 64 ? 1 : -1, [&](auto w64) {
+        return lift<CRC_GPU_MAX_LOG2G + 1>(k.lg, [&](auto lg) {
+            return lift<kOffsets + 1>(k.mode, [&](auto mode) {
+                return lift<kOpUnpack + 1>(k.op, [&](auto op) {
+                    return lift<2>(k.nt, [&](auto nt) {
+                        return lift<2>(k.light, [&](auto light) {
+                            return lift<2>(k.split, [&](auto split) {
+                                return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0, split() != 0>();
+                            });
+                        });
+                    });
+                });
+            });
+        });
+    });
 }
 
-template <int W>
-KLaunch fixed_kernel(const LaunchPlan &p) {
-    switch (p.lg) {
-        case 0: return fixed_kernel_lg<W, 0>(p);
-        case 1: return fixed_kernel_lg<W, 1>(p);
-        case 2: return fixed_kernel_lg<W, 2>(p);
-        case 3: return fixed_kernel_lg<W, 3>(p);
-        case 4: return fixed_kernel_lg<W, 4>(p);
-        case 5: return fixed_kernel_lg<W, 5>(p);
-        default: return fixed_kernel_lg<W, 6>(p);
-    }
-}
+// One offsets-shaped call, as its entry point names it.  The payloads (or,
+// with msg, the messages that hold them) lie at src by the table src_off.
+struct OffsetsCall {
+    BatchOp op;
+    const char *method;
+    const void *src;
+    const uint64_t *src_off;
+    size_t count;
+    void *out = nullptr;                 // checksum: the CRCs; update: the running registers; seal: src, writable
+    void *dst = nullptr;                 // pack, unpack: where the payloads are copied to, by the table dst_off
+    const uint64_t *dst_off = nullptr;
+    const void *expected = nullptr;      // verify_offsets
+    uint8_t *status = nullptr;
+    uint32_t *mismatches = nullptr;
+    bool msg = false;                    // message mode: payload_offset, hash_offset
+    size_t pay_off = 0, hash_off = 0;
+    void *stream = nullptr;
+};
 
-// The kernel a plan (launch_plan.h) launches; verify: it compares with the
-// expected values instead of storing its own; seed (offsets plans): it
-// advances running registers instead; sender (CRC-32C offsets plans): it seals,
-// packs or unpacks messages.
-KLaunch kernel_for(const LaunchPlan &p, bool verify, bool seed = false, int sender = kNoSender) {
-    if (p.mode == kOffsets && sender == kUnpack) return unpack_kernel(p);
-    if (p.mode == kOffsets && sender != kNoSender) return sender == kPack ? sender_kernel<true>(p) : sender_kernel<false>(p);
-    if (p.mode == kOffsets)
-        return p.width == 32 ? offsets_kernel<32>(p, verify, seed) : offsets_kernel<64>(p, verify, seed);
-    if (p.split)
-        return p.nt ? kernel_ptr<64, 6, kFixedAligned, false, true, false, true>()
-                    : kernel_ptr<64, 6, kFixedAligned, false, false, false, true>();
-    return p.width == 32 ? fixed_kernel<32>(p) : fixed_kernel<64>(p);
-}
-
-int do_offsets(const char *method, const void *base, const uint64_t *offsets, size_t count, void *out,
-               const void *expected, uint8_t *status, uint32_t *mism, void *stream, bool verify,
-               bool msg = false, size_t pay_off = 0, size_t hash_off = 0, bool seed = false) {
-    // seed (update_offsets): `out` is the running-register array, advanced in
-    // place by the seeded twin of the kernel the same plan picks
+// The front of every offsets-shaped entry point: argument checks, model,
+// device context, plan, table pack, BatchArgs, slot and launch.  The calls on
+// HG messages (seal, pack, unpack) check the method ahead of the device, as an
+// argument (as verify_core_headers does); the others the device first.
+int offsets_call(const OffsetsCall &c) {
+    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal;
+    const bool stores = c.op == kOpChecksum || c.op == kOpUpdate || c.op == kOpSeal;
     // an empty batch needs no buffers (not even the one-entry offsets table)
-    if (count && (!base || !offsets || (!verify && !out) || (verify && !msg && !expected)))
+    if (c.count && (!c.src || !c.src_off || (stores && !c.out) || (copies && (!c.dst || !c.dst_off)) ||
+                    (c.op == kOpVerify && !c.msg && !c.expected)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
-    if (msg && (hash_off + 4 > pay_off || pay_off > (1u << 30)))
+    if (c.msg && (c.hash_off + 4 > c.pay_off || c.pay_off > (1u << 30)))
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
-    if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
-    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    if ((uint64_t)c.count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
     Model m;
-    DevCtx *c = nullptr;
-    const void *pack = nullptr;
-    int rc = resolve_model(method, &m);
-    if (!rc) rc = device_ctx(&c);
-    if (rc) return rc;
-    const LaunchPlan p = plan_offsets(*mck_settings(), c->cus, m.width, count);
-    if ((rc = get_pack(c, m.idx, p.lg, &pack))) return rc;
-    const void *shift = nullptr;
-    if (seed && (rc = get_ext(c, m.idx, &shift))) return rc;
-    if (count == 0) return MCHECKSUM_GPU_OK;
-    if (msg && m.width != 32)
+    int rc;
+    if (hg) {
+        if ((rc = resolve_model(c.method, &m))) return rc;
+        if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
+    }
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    if (!hg && (rc = resolve_model(c.method, &m))) return rc;
+    DevCtx *dc = nullptr;
+    const void *pack = nullptr, *shift = nullptr;
+    if ((rc = device_ctx(&dc))) return rc;
+    const LaunchPlan p = plan_offsets(*mck_settings(), dc->cus, m.width, c.count);
+    // (an empty batch too resolves its method and builds its tables)
+    if ((rc = get_pack(dc, m.idx, p.lg, &pack))) return rc;
+    if (c.op == kOpUpdate && (rc = get_ext(dc, m.idx, &shift))) return rc;
+    if (c.count == 0) return MCHECKSUM_GPU_OK;
+    if (c.msg && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
+    const KLaunch k = kernel_for(kernel_key(p, c.op));
+    if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     BatchArgs a{};
-    a.base = (const uint8_t *)base;
-    a.offsets = offsets;
-    a.count = count;
-    a.out = out;
-    a.expected = expected;
-    a.status = status;
-    a.mismatches = mism;
+    a.base = (const uint8_t *)c.src;
+    a.offsets = c.src_off;
+    a.count = c.count;
+    a.out = copies ? c.dst : c.out;
+    if (copies) a.dst_offsets = c.dst_off;
+    else a.expected = c.expected;
+    a.status = c.status;
+    a.mismatches = c.mismatches;
     a.pack = pack;
-    a.msg = msg ? 1u : 0u;
-    a.pay_off = (uint32_t)pay_off;
-    a.hash_off = (uint32_t)hash_off;
-    a.err_word = t_err_word;
-    a.bswap = verify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
+    a.msg = c.msg ? 1u : 0u;
+    a.pay_off = (uint32_t)c.pay_off;
+    a.hash_off = (uint32_t)c.hash_off;
+    a.err_word = error_word();
+    a.bswap = c.op == kOpVerify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
     a.shift = shift;
-    const KLaunch k = kernel_for(p, verify, seed);
     SlotRef sr;
-    if (p.dyn) sr = queue_slot(c, stream);
+    if (p.dyn) sr = queue_slot(dc, c.stream);
     a.queue = sr.q;
-    rc = launch_slot(c, sr, k.k, p.grid, k.block, stream, a, "kernel launch");
-    // (registers stay in the kernels' form: state_get swaps an MSB-first model's)
-    if (rc == MCHECKSUM_GPU_OK && m.msb && !verify && !seed) rc = swap_outputs(out, count, m.width, stream);
+    static const char *const what[] = {"kernel launch",      "kernel launch",      "kernel launch",
+                                       "seal kernel launch", "pack kernel launch", "unpack kernel launch"};
+    rc = launch_slot(dc, sr, k.k, p.grid, k.block, c.stream, a, what[c.op]);
+    // (running registers stay in the kernels' form: state_get swaps an MSB-first model's)
+    if (rc == MCHECKSUM_GPU_OK && m.msb && c.op == kOpChecksum) rc = swap_outputs(c.out, c.count, m.width, c.stream);
     return rc;
-}
-
-// seal_messages (src == nullptr: in place, the payloads are dev_buf's own),
-// pack_messages (payload i = src[src_off[i], src_off[i+1]) goes behind the
-// headers of message i of dev_buf) and unpack_messages (pack's mirror: src is
-// the message buffer with its table, buf the destination with its table, and
-// the launch counts mismatches into mism).  verify_messages' argument checks
-// in its order, with the method check ahead of the device's (an argument
-// check, as in verify_core_headers); then the same plan, queue rules and launch.
-int do_sender(const char *method, const void *src, const uint64_t *src_off, void *buf, const uint64_t *msg_off,
-              size_t count, size_t pay_off, size_t hash_off, uint8_t *status, void *stream, int kind,
-              uint32_t *mism = nullptr) {
-    const bool pack = kind != kSeal;  // two buffers, two tables
-    if (count && (!buf || !msg_off || (pack && (!src || !src_off))))
-        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
-    if (hash_off + 4 > pay_off || pay_off > (1u << 30))
-        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
-    if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
-    Model m;
-    int rc = resolve_model(method, &m);
-    if (rc) return rc;
-    if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
-    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
-    DevCtx *c = nullptr;
-    const void *tables = nullptr;
-    if ((rc = device_ctx(&c))) return rc;
-    const LaunchPlan p = plan_offsets(*mck_settings(), c->cus, m.width, count);
-    if ((rc = get_pack(c, m.idx, p.lg, &tables))) return rc;
-    if (count == 0) return MCHECKSUM_GPU_OK;
-    BatchArgs a{};
-    a.base = (const uint8_t *)(pack ? src : buf);
-    a.offsets = pack ? src_off : msg_off;
-    a.count = count;
-    a.out = buf;
-    a.expected = pack ? msg_off : nullptr;  // the COPY twins' destination table
-    a.status = status;
-    a.mismatches = mism;
-    a.pack = tables;
-    a.msg = 1u;
-    a.pay_off = (uint32_t)pay_off;
-    a.hash_off = (uint32_t)hash_off;
-    a.err_word = t_err_word;
-    const KLaunch k = kernel_for(p, kind == kUnpack, false, kind);
-    SlotRef sr;
-    if (p.dyn) sr = queue_slot(c, stream);
-    a.queue = sr.q;
-    return launch_slot(c, sr, k.k, p.grid, k.block, stream, a,
-                       kind == kUnpack ? "unpack kernel launch" : pack ? "pack kernel launch" : "seal kernel launch");
 }
 
 // ---- streaming state: 256-thread element kernels (grid: elem_grid) ----
@@ -558,14 +500,15 @@ int launch_fixed(DevCtx *c, const Model &m, const LaunchPlan &p, const void *pac
     a.count = count;
     a.out = dev_out;
     a.pack = pack;
-    a.err_word = t_err_word;
+    a.err_word = error_word();
     if (p.split) {
         const void *shift = nullptr;
         if (int rc = get_ext(c, m.idx, &shift)) return rc;
         a.shift = shift;
         a.split_log2 = p.split_log2;
     }
-    const KLaunch k = kernel_for(p, false);
+    const KLaunch k = kernel_for(kernel_key(p, kOpChecksum));
+    if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     SlotRef sr;
     if (p.dyn) sr = queue_slot(c, stream);
     a.queue = sr.q;
@@ -659,42 +602,78 @@ int mchecksum_gpu_checksum_fixed(const char *hash_method, const void *dev_base, 
 
 int mchecksum_gpu_checksum_offsets(const char *hash_method, const void *dev_base, const uint64_t *dev_offsets,
                                    size_t count, void *dev_out, void *stream) {
-    return do_offsets(hash_method, dev_base, dev_offsets, count, dev_out, nullptr, nullptr, nullptr, stream, false);
+    OffsetsCall c{kOpChecksum, hash_method, dev_base, dev_offsets, count};
+    c.out = dev_out;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_verify_offsets(const char *hash_method, const void *dev_base, const uint64_t *dev_offsets,
                                  size_t count, const void *dev_expected, uint8_t *dev_status,
                                  uint32_t *dev_mismatches, void *stream) {
-    return do_offsets(hash_method, dev_base, dev_offsets, count, nullptr, dev_expected, dev_status,
-                      dev_mismatches, stream, true);
+    OffsetsCall c{kOpVerify, hash_method, dev_base, dev_offsets, count};
+    c.expected = dev_expected;
+    c.status = dev_status;
+    c.mismatches = dev_mismatches;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf, const uint64_t *dev_msg_offsets,
                                   size_t count, size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
                                   uint32_t *dev_mismatches, void *stream) {
-    return do_offsets(hash_method, dev_buf, dev_msg_offsets, count, nullptr, nullptr, dev_status, dev_mismatches,
-                      stream, true, true, payload_offset, hash_offset);
+    OffsetsCall c{kOpVerify, hash_method, dev_buf, dev_msg_offsets, count};
+    c.msg = true;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_mismatches;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
                                 size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
-    return do_sender(hash_method, nullptr, nullptr, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
-                     dev_status, stream, kSeal);
+    OffsetsCall c{kOpSeal, hash_method, dev_buf, dev_msg_offsets, count};  // in place: the payloads are dev_buf's own
+    c.out = dev_buf;
+    c.msg = true;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_pack_messages(const char *hash_method, const void *dev_src, const uint64_t *dev_src_offsets,
                                 void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                 size_t hash_offset, uint8_t *dev_status, void *stream) {
-    return do_sender(hash_method, dev_src, dev_src_offsets, dev_buf, dev_msg_offsets, count, payload_offset,
-                     hash_offset, dev_status, stream, kPack);
+    // payload i = src[src_off[i], src_off[i+1]) goes behind the headers of message i of dev_buf
+    OffsetsCall c{kOpPack, hash_method, dev_src, dev_src_offsets, count};
+    c.dst = dev_buf;
+    c.dst_off = dev_msg_offsets;
+    c.msg = true;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_unpack_messages(const char *hash_method, const void *dev_buf, const uint64_t *dev_msg_offsets,
                                   size_t count, size_t payload_offset, size_t hash_offset, void *dev_dst,
                                   const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_mismatches,
                                   void *stream) {
-    return do_sender(hash_method, dev_buf, dev_msg_offsets, dev_dst, dev_dst_offsets, count, payload_offset,
-                     hash_offset, dev_status, stream, kUnpack, dev_mismatches);
+    // pack's mirror: the messages are the source, and the launch counts mismatches
+    OffsetsCall c{kOpUnpack, hash_method, dev_buf, dev_msg_offsets, count};
+    c.dst = dev_dst;
+    c.dst_off = dev_dst_offsets;
+    c.msg = true;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_mismatches;
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {
@@ -715,8 +694,10 @@ int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t co
 
 int mchecksum_gpu_update_offsets(const char *hash_method, const void *dev_base, const uint64_t *dev_offsets,
                                  size_t count, void *dev_state, void *stream) {
-    return do_offsets(hash_method, dev_base, dev_offsets, count, dev_state, nullptr, nullptr, nullptr, stream, false,
-                      false, 0, 0, true);
+    OffsetsCall c{kOpUpdate, hash_method, dev_base, dev_offsets, count};
+    c.out = dev_state;  // advanced in place by the seeded twin of the checksum kernel the same plan picks
+    c.stream = stream;
+    return offsets_call(c);
 }
 
 int mchecksum_gpu_state_get(const char *hash_method, const void *dev_state, size_t count, void *dev_out,

@@ -3,7 +3,9 @@
 // was taken from the scattered decision functions this header replaced (a
 // differential sweep over ~800 000 shapes agreed with them in every field),
 // so an edit that moves a threshold, a lane count or a grid fails here, on the
-// CPU.  Plain C++: no HIP header.
+// CPU.  So does one that changes which kernel a plan leads to for the call's
+// operation (kernel_key), or which kernels there are (kernel_key_valid).
+// Plain C++: no HIP header.
 #include "launch_plan.h"
 
 #include <cstdio>
@@ -132,6 +134,113 @@ static const OffsetsRow kOffsetsRows[] = {
     {"cus 8", D, 8, 64, 8192, /**/ 0, 1, 1, 8192ull, 1024, 2, 16},
 };
 
+// The kernel a plan leads to for the call's operation (kernel_key): the
+// expected KernelKey is {width, lg, mode, op, nt, light, split}.
+struct OffsetsKeyRow {
+    const char *name;
+    Set set;
+    int width;
+    size_t count;
+    BatchOp op;
+    KernelKey key;
+};
+#define OP_ROWS32(OP)                                                                                   \
+    {#OP " crc32c x 1024: light", D, 32, 1024, OP, {32, 6, kOffsets, OP, 0, 1, 0}},                     \
+    {#OP " crc32c x 1025: full", D, 32, 1025, OP, {32, 6, kOffsets, OP, 0, 0, 0}},                      \
+    {#OP " crc32c x 8191: full", D, 32, 8191, OP, {32, 6, kOffsets, OP, 0, 0, 0}},                      \
+    {#OP " crc32c x 8192: nt", D, 32, 8192, OP, {32, 6, kOffsets, OP, 1, 0, 0}},                        \
+    {#OP " gpu_light 0 at 1024: full", LIGHT0, 32, 1024, OP, {32, 6, kOffsets, OP, 0, 0, 0}},           \
+    {#OP " gpu_light 1 at 8192: light, no nt form", LIGHT1, 32, 8192, OP, {32, 6, kOffsets, OP, 0, 1, 0}}, \
+    {#OP " gpu_nt 0 at 8192: full", NT0, 32, 8192, OP, {32, 6, kOffsets, OP, 0, 0, 0}},                 \
+    {#OP " gpu_nt 1 at 1025: nt", NT1, 32, 1025, OP, {32, 6, kOffsets, OP, 1, 0, 0}},                   \
+    {#OP " gpu_nt 1 at 1024: light, no nt form", NT1, 32, 1024, OP, {32, 6, kOffsets, OP, 0, 1, 0}}
+#define OP_ROWS64(OP)                                                                                   \
+    {#OP " crc64 x 1024: full", D, 64, 1024, OP, {64, 6, kOffsets, OP, 0, 0, 0}},                       \
+    {#OP " crc64 x 1025: full", D, 64, 1025, OP, {64, 6, kOffsets, OP, 0, 0, 0}},                       \
+    {#OP " crc64 x 8191: full", D, 64, 8191, OP, {64, 6, kOffsets, OP, 0, 0, 0}},                       \
+    {#OP " crc64 x 8192: nt", D, 64, 8192, OP, {64, 6, kOffsets, OP, 1, 0, 0}},                         \
+    {#OP " crc64, gpu_light 0 at 1024", LIGHT0, 64, 1024, OP, {64, 6, kOffsets, OP, 0, 0, 0}},          \
+    {#OP " crc64, gpu_light 1 at 1024: no light form", LIGHT1, 64, 1024, OP, {64, 6, kOffsets, OP, 0, 0, 0}}, \
+    {#OP " crc64, gpu_nt 0 at 8192", NT0, 64, 8192, OP, {64, 6, kOffsets, OP, 0, 0, 0}},                \
+    {#OP " crc64, gpu_nt 1 at 1024", NT1, 64, 1024, OP, {64, 6, kOffsets, OP, 1, 0, 0}}
+static const OffsetsKeyRow kOffsetsKeys[] = {
+    OP_ROWS32(kOpChecksum), OP_ROWS32(kOpVerify), OP_ROWS32(kOpUpdate), OP_ROWS32(kOpSeal), OP_ROWS32(kOpPack),
+    OP_ROWS32(kOpUnpack),   OP_ROWS64(kOpChecksum), OP_ROWS64(kOpVerify), OP_ROWS64(kOpUpdate),
+};
+#undef OP_ROWS32
+#undef OP_ROWS64
+
+// (fixed batches are checksums)
+struct FixedKeyRow {
+    const char *name;
+    Set set;
+    int width;
+    uintptr_t base;
+    size_t len, count;
+    KernelKey key;
+};
+static const FixedKeyRow kFixedKeys[] = {
+    {"headline", D, 32, A, 65536, 65536, {32, 6, kFixedAligned, kOpChecksum, 1, 0, 0}},
+    {"C2", D, 32, A, 4096, 65536, {32, 4, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"C3: split, nt", D, 64, A, 1048576, 8192, {64, 6, kFixedAligned, kOpChecksum, 1, 0, 1}},
+    {"light 1024 x 4 KiB", D, 32, A, 4096, 1024, {32, 6, kFixedAligned, kOpChecksum, 0, 1, 0}},
+    {"light 4096 x 4 KiB", D, 32, A, 4096, 4096, {32, 4, kFixedAligned, kOpChecksum, 0, 1, 0}},
+    {"full 4097 x 4 KiB", D, 32, A, 4096, 4097, {32, 6, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"nt, 131072 x 4 KiB", D, 32, A, 4096, 131072, {32, 4, kFixedAligned, kOpChecksum, 1, 0, 0}},
+    {"not nt, 131071 x 4 KiB", D, 32, A, 4096, 131071, {32, 4, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"misaligned headline: generic, no nt form", D, 32, A + 8, 65536, 65536, {32, 6, kFixedGeneric, kOpChecksum, 0, 0, 0}},
+    {"light generic", D, 32, A, 4112, 1024, {32, 6, kFixedGeneric, kOpChecksum, 0, 1, 0}},
+    {"crc64 misaligned C3: generic", D, 64, A + 8, 1048576, 8192, {64, 6, kFixedGeneric, kOpChecksum, 0, 0, 0}},
+    {"crc64 1024 x 4 KiB", D, 64, A, 4096, 1024, {64, 6, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"crc64 64 KiB x 65536: 32 lanes, nt", D, 64, A, 65536, 65536, {64, 5, kFixedAligned, kOpChecksum, 1, 0, 0}},
+    {"gpu_log2g 0 on C2", LG0, 32, A, 4096, 65536, {32, 0, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"gpu_light 0 on 1024 x 4 KiB", LIGHT0, 32, A, 4096, 1024, {32, 6, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"gpu_light 1 on the headline: light, no nt form", LIGHT1, 32, A, 65536, 65536, {32, 0, kFixedAligned, kOpChecksum, 0, 1, 0}},
+    {"gpu_light 1 leaves crc64 alone", LIGHT1, 64, A, 4096, 1024, {64, 6, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"gpu_nt 0 on the headline", NT0, 32, A, 65536, 65536, {32, 6, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"gpu_nt 1 on C2", NT1, 32, A, 4096, 65536, {32, 4, kFixedAligned, kOpChecksum, 1, 0, 0}},
+    {"gpu_nt 1 on 64 x 4 KiB: light, no nt form", NT1, 32, A, 4096, 64, {32, 6, kFixedAligned, kOpChecksum, 0, 1, 0}},
+    {"gpu_nt 1 on the misaligned headline: generic, no nt form", NT1, 32, A + 8, 65536, 65536, {32, 6, kFixedGeneric, kOpChecksum, 0, 0, 0}},
+    {"gpu_split 0 on C3", SPLIT0, 64, A, 1048576, 8192, {64, 6, kFixedAligned, kOpChecksum, 1, 0, 0}},
+    {"gpu_split 1 on 3 x 512 KiB crc64: split, not nt", SPLIT1, 64, A, 524288, 3, {64, 6, kFixedAligned, kOpChecksum, 0, 0, 1}},
+    {"gpu_force_generic 1 on C3", GENERIC, 64, A, 1048576, 8192, {64, 6, kFixedGeneric, kOpChecksum, 0, 0, 0}},
+};
+
+// kernel_key_valid: no kernel has these forms
+static const struct {
+    const char *name;
+    KernelKey key;
+} kNoKernel[] = {
+    {"update of a fixed batch", {32, 6, kFixedAligned, kOpUpdate, 0, 0, 0}},
+    {"update below 64 lanes", {32, 5, kOffsets, kOpUpdate, 0, 0, 0}},
+    {"crc64 update of a fixed batch", {64, 6, kFixedGeneric, kOpUpdate, 0, 0, 0}},
+    {"crc64 update below 64 lanes", {64, 0, kOffsets, kOpUpdate, 0, 0, 0}},
+    {"crc64 update of split pieces", {64, 6, kFixedAligned, kOpUpdate, 1, 0, 1}},
+    {"seal of a fixed batch", {32, 6, kFixedAligned, kOpSeal, 0, 0, 0}},
+    {"seal below 64 lanes", {32, 4, kOffsets, kOpSeal, 0, 1, 0}},
+    {"crc64 seal", {64, 6, kOffsets, kOpSeal, 0, 0, 0}},
+    {"pack of a fixed batch", {32, 6, kFixedGeneric, kOpPack, 0, 0, 0}},
+    {"pack below 64 lanes", {32, 3, kOffsets, kOpPack, 1, 0, 0}},
+    {"crc64 pack", {64, 6, kOffsets, kOpPack, 1, 0, 0}},
+    {"unpack of a fixed batch", {32, 6, kFixedAligned, kOpUnpack, 1, 0, 0}},
+    {"unpack below 64 lanes", {32, 5, kOffsets, kOpUnpack, 0, 0, 0}},
+    {"crc64 unpack", {64, 6, kOffsets, kOpUnpack, 0, 0, 0}},
+    {"verify of a fixed batch", {32, 6, kFixedAligned, kOpVerify, 0, 0, 0}},
+    {"verify of split pieces", {64, 6, kFixedAligned, kOpVerify, 1, 0, 1}},
+    {"split below 64 lanes", {64, 5, kFixedAligned, kOpChecksum, 1, 0, 1}},
+    {"split generic", {64, 6, kFixedGeneric, kOpChecksum, 0, 0, 1}},
+    {"split offsets", {64, 6, kOffsets, kOpChecksum, 0, 0, 1}},
+    {"split crc32c", {32, 6, kFixedAligned, kOpChecksum, 1, 0, 1}},
+    {"offsets checksum below 64 lanes", {32, 5, kOffsets, kOpChecksum, 0, 0, 0}},
+    {"light with nt", {32, 6, kOffsets, kOpChecksum, 1, 1, 0}},
+    {"light crc64", {64, 6, kOffsets, kOpChecksum, 0, 1, 0}},
+    {"generic with nt", {32, 6, kFixedGeneric, kOpChecksum, 1, 0, 0}},
+    {"no such width", {16, 6, kOffsets, kOpChecksum, 0, 0, 0}},
+    {"no such lane count", {32, 7, kFixedAligned, kOpChecksum, 0, 0, 0}},
+    {"no such mode", {32, 6, 3, kOpChecksum, 0, 0, 0}},
+    {"no such operation", {32, 6, kOffsets, kOpUnpack + 1, 0, 0, 0}},
+};
+
 // choose_log2g(width, len) with nothing forced
 static const struct {
     int width;
@@ -216,6 +325,58 @@ int main() {
         const LaunchPlan p = plan_offsets(s, r.cus, r.width, r.count);
         check_offsets(r, p);
         pack_use[p.lg]++;
+    }
+    // the kernel each plan leads to
+    auto same_key = [](const char *name, const KernelKey &k, const KernelKey &want) {
+        CHECK(k == want && kernel_key_valid(k), "%s: key {%d, %d, %d, %d, nt %d, light %d, split %d}%s", name, k.width, k.lg,
+              k.mode, k.op, k.nt, k.light, k.split, kernel_key_valid(k) ? "" : " (not valid)");
+    };
+    for (const OffsetsKeyRow &r : kOffsetsKeys)
+        same_key(r.name, kernel_key(plan_offsets(r.set.snapshot(), 256, r.width, r.count), r.op), r.key);
+    for (const FixedKeyRow &r : kFixedKeys)
+        same_key(r.name, kernel_key(plan_fixed(r.set.snapshot(), 256, r.width, r.base, r.len, r.len, r.count), kOpChecksum), r.key);
+    for (const auto &r : kNoKernel) CHECK(!kernel_key_valid(r.key), "%s: valid", r.name);
+    // what a plan says of the batch and the kernel has no form for is dropped
+    {
+        LaunchPlan p;
+        p.width = 64, p.lg = 3, p.mode = kOffsets, p.nt = true, p.light = true;
+        same_key("hand-made crc64 offsets plan", kernel_key(p, kOpVerify), {64, 6, kOffsets, kOpVerify, 1, 0, 0});
+        p.width = 32;
+        same_key("hand-made light offsets plan", kernel_key(p, kOpSeal), {32, 6, kOffsets, kOpSeal, 0, 1, 0});
+        p.mode = kFixedGeneric, p.light = false;
+        same_key("hand-made generic plan", kernel_key(p, kOpChecksum), {32, 3, kFixedGeneric, kOpChecksum, 0, 0, 0});
+        p.split = true;
+        same_key("hand-made split plan", kernel_key(p, kOpChecksum), {64, 6, kFixedAligned, kOpChecksum, 1, 0, 1});
+    }
+    // Every plan of the tables above, with every operation: a key is valid
+    // exactly when the operation is one the plan's kind of batch has (fixed
+    // batches: checksums; offsets batches: all six for CRC-32C, no seal, pack
+    // or unpack for CRC-64).
+    for (int op = kOpChecksum; op <= kOpUnpack; op++) {
+        for (const FixedRow &r : kFixed) {
+            const LaunchPlan p = plan_fixed(r.set.snapshot(), r.cus, r.width, r.base, r.stride, r.len, r.count);
+            CHECK(kernel_key_valid(kernel_key(p, (BatchOp)op)) == (op == kOpChecksum), "%s, op %d: valid key", r.name, op);
+        }
+        for (const OffsetsRow &r : kOffsetsRows) {
+            const LaunchPlan p = plan_offsets(r.set.snapshot(), r.cus, r.width, r.count);
+            CHECK(kernel_key_valid(kernel_key(p, (BatchOp)op)) == (op <= kOpUpdate || r.width == 32), "%s, op %d: valid key",
+                  r.name, op);
+        }
+    }
+    // ... and how many kernels that makes: 35 fixed CRC-32C, 21 fixed CRC-64,
+    // 2 split, 15 offsets checksum / verify / update, 9 seal / pack / unpack
+    {
+        int n[5] = {};
+        for (int width : {16, 32, 64})
+            for (int lg = -1; lg <= CRC_GPU_MAX_LOG2G + 1; lg++)
+                for (int mode = -1; mode <= kOffsets + 1; mode++)
+                    for (int op = -1; op <= kOpUnpack + 1; op++)
+                        for (int f = 0; f < 8; f++) {
+                            const KernelKey k{width, lg, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0};
+                            if (kernel_key_valid(k)) n[k.split ? 2 : mode != kOffsets ? (width == 64) : op <= kOpUpdate ? 3 : 4]++;
+                        }
+        CHECK(n[0] == 35 && n[1] == 21 && n[2] == 2 && n[3] == 15 && n[4] == 9, "valid keys: %d %d %d %d %d", n[0], n[1], n[2],
+              n[3], n[4]);
     }
     const mck_settings_t d = D.snapshot();
     for (const auto &r : kLanes) CHECK(choose_log2g(d, r.len, r.width) == r.lg, "choose_log2g(%zu, %d) = %d", r.len, r.width, choose_log2g(d, r.len, r.width));

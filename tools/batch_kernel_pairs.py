@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Pairs the batch kernels of two builds of mchecksum_gpu.hip by what they are
+-- (width, lanes, mode, operation, NT, light, split) -- instead of by name, and
+compares each pair: registers, scratch, LDS, occupancy, code size and the
+instruction stream.  For a change that renames the kernels' template
+parameters and must leave their machine code alone.
+
+Each build is a directory holding what `make asm` leaves: resource_usage.txt
+and the device assembly mchecksum_gpu-hip-amdgcn-amd-amdhsa-gfx950.s.
+
+usage: batch_kernel_pairs.py OLD_DIR NEW_DIR
+
+A kernel's key is read from its demangled template arguments, in either
+spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
+and crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED> (bool packs), or
+<LOG2G, MODE, OP, NT, LIGHT> and <LOG2G, MODE, OP, NT, SPLIT> (BatchOp,
+launch_plan.h).  Exit status 1 unless the pairing is one to one and every pair
+is equal in everything.
+"""
+import hashlib
+import os
+import re
+import subprocess
+import sys
+
+from resource_diff import KEYS, parse
+
+OPS = ["checksum", "verify", "update", "seal", "pack", "unpack"]
+MODES = ["aligned", "generic", "offsets"]
+ASM = "mchecksum_gpu-hip-amdgcn-amd-amdhsa-gfx950.s"
+
+
+def key_of(name):
+    """(width, lg, mode, op, nt, light, split) of a demangled batch kernel name, else None."""
+    m = re.search(r"crc(32c|64)_batch_kernel<([^>]*)>", name)
+    if not m:
+        return None
+    width = 32 if m.group(1) == "32c" else 64
+    a = [{"true": 1, "false": 0}.get(t.strip(), t.strip()) for t in m.group(2).split(",")]
+    a = [int(re.sub(r"^\(.*\)", "", t)) if isinstance(t, str) else t for t in a]
+    lg, mode = a[0], a[1]
+    if len(a) == 5:  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT>
+        op, nt, last = a[2], a[3], a[4]
+        light, split = (last, 0) if width == 32 else (0, last)
+    else:  # the bool packs
+        verify, nt = a[2], a[3]
+        if width == 32:
+            light, seed, seal, copy = a[4:8]
+            split = 0
+        else:
+            split, seed = a[4:6]
+            light = seal = copy = 0
+        op = 2 if seed else 4 if seal and copy else 3 if seal else 5 if verify and copy else 1 if verify else 0
+    return (width, lg, MODES[mode], OPS[op], nt, light, split)
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return dict(zip(names, out))
+
+
+def streams(path):
+    """Per function of a device .s file: (sha1 of its instruction stream, instruction count, code bytes)."""
+    body, name, last, out = None, None, None, {}
+    for line in open(path, errors="replace"):
+        if body is None:
+            m = re.match(r"\s*\.type\s+([^,]+),@function", line)
+            if m:
+                name, body = m.group(1), []
+            elif last and "codeLenInByte" in line:
+                out[last][2] = int(line.split("=")[1])
+                last = None
+            continue
+        if line.startswith(".Lfunc_end"):
+            out[name] = [hashlib.sha1("\n".join(body).encode()).hexdigest()[:16], sum(not s.endswith(":") for s in body), None]
+            last, body = name, None
+            continue
+        s = line.split(";")[0].strip()
+        # directives (debug line information among them) and temporary labels are no instructions
+        if not s or (s.startswith(".") and not re.match(r"\.LBB\d+_\d+:", s)) or re.match(r"\.?Ltmp\d+:", s):
+            continue
+        s = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s)
+        s = re.sub(r"\b_Z\w*_batch_kernel\w*", "SYMBOL", s)  # the kernels' names carry their template arguments
+        body.append(s)
+    return out
+
+
+def load(d):
+    res = parse(os.path.join(d, "resource_usage.txt"))  # keyed by demangled name
+    asm = streams(os.path.join(d, ASM))
+    names = demangle(list(asm))
+    rows = {}
+    for mangled, (sha, n, size) in asm.items():
+        short = re.sub(r"\(anonymous namespace\)::|^void ", "", names[mangled])
+        k = key_of(short)
+        if k is None:  # the element kernels and the device functions the batch kernels call: by name
+            short = re.sub(r"\(.*\)$", "", short)
+            k = (0, 0, "-", short, 0, 0, 0)
+        elif not short.startswith("crc"):  # a function one batch kernel did not inline: by that kernel and its own name
+            k = k + (short.split("<")[0],)
+        else:
+            short = re.sub(r"\(.*\)$", "", short)
+        if k in rows:
+            sys.exit(f"{d}: two functions with key {k}")
+        rows[k] = dict(sha=sha, insts=n, code=size, res=[res.get(short, {}).get(x, "-") for x in KEYS])
+    return rows
+
+
+def main():
+    old, new = load(sys.argv[1]), load(sys.argv[2])
+    bad = 0
+    print("width lanes mode operation nt light split | " + " | ".join(KEYS) + " | code bytes | instructions | stream sha1 | verdict")
+    for k in sorted(set(old) | set(new)):
+        label = f"{k[0]} {1 << k[1]} {k[2]} {k[3]} {k[4]} {k[5]} {k[6]}" + (f" ({k[7]}, not inlined)" if len(k) > 7 else "")
+        if k not in old or k not in new:
+            print(f"{label} | only in the {'new' if k in new else 'old'} build")
+            bad += 1
+            continue
+        o, n = old[k], new[k]
+        same = o["res"] == n["res"] and o["code"] == n["code"] and o["sha"] == n["sha"] and o["code"] is not None
+        bad += not same
+        print(f"{label} | " + " | ".join(n["res"]) + f" | {n['code']} | {n['insts']} | {n['sha']} | " +
+              ("same" if same else f"DIFFERS (old: {' '.join(o['res'])} | {o['code']} | {o['insts']} | {o['sha']})"))
+    print(f"{len(old)} kernels in the old build, {len(new)} in the new, {len(set(old) & set(new))} paired, {bad} differ or are unpaired")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
