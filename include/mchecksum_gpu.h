@@ -183,6 +183,65 @@ mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a,
     const void *dev_crc_b, const uint64_t *dev_len_b, size_t count,
     void *dev_out, void *stream);
 
+/* Copy and checksum in one pass: many device-resident chunks are copied to
+ * independent destinations and hashed in the same read -- a chunk of a bulk
+ * transfer hashed in its staging buffer and moved to its place in the object,
+ * without a second pass over its bytes.  A one-shot form and a streaming form.
+ *
+ * Chunk i = dev_src[dev_src_offsets[i], dev_src_offsets[i+1]) (the
+ * checksum_offsets layout and memory rules: count + 1 non-decreasing byte
+ * offsets, any start byte, readable to the next 16-byte boundary), n_i bytes.
+ * It is copied to dev_dst[dev_dst_starts[i], dev_dst_starts[i] + n_i).
+ * dev_dst_starts holds `count` byte offsets into dev_dst, in any order:
+ * destinations need not be adjacent or monotonic, so there is no fit rule and
+ * no status array; the length of each copy comes from the source table.
+ *
+ *   - The values are those of mchecksum_gpu_checksum_offsets, and the state
+ *     rules those of mchecksum_gpu_update_offsets, bit for bit; every 32/64-bit
+ *     catalogue method.
+ *   - A zero-length chunk writes nothing and leaves its state unchanged.
+ *   - Exactly the n_i destination bytes of each chunk are written: no byte
+ *     before them, after them or between them, so dev_dst needs no padding.
+ *   - dev_src is never written.
+ *   - Destination ranges must not overlap one another or the source range.  The
+ *     library cannot check this (the tables are on the device): an overlapping
+ *     call copies and hashes unspecified bytes.
+ *   - Chunks of any size, 2 GiB and more included.
+ *   - Asynchronous and stream-ordered; capture-safe after
+ *     mchecksum_gpu_prepare().  A replay copies and hashes the current contents
+ *     again, and a replayed update advances the state again.
+ *   - Launch plan, work-queue slot and static-split rules are those of
+ *     checksum_offsets / update_offsets for the same count.
+ *   - MSB-first methods: copy_offsets swaps its outputs after the launch, as
+ *     checksum_offsets does; states stay in the kernels' form.
+ *   - Fail closed as update_offsets: a call in which a device wait gave up adds
+ *     1 -- once per call -- to the error word and to
+ *     mchecksum_gpu_queue_faults(); after such a call the outputs, the states
+ *     and the destination bytes it touched are unspecified.
+ *   - Arguments are checked in checksum_offsets' order: NULL pointers and
+ *     count > 2^31 (MCHECKSUM_GPU_EINVAL), then the device (_ENODEV), then the
+ *     method (_EMETHOD: unknown, or 16-bit).  count == 0 needs no buffers, but
+ *     passes those checks first.
+ *   - CRC-32C: the fused call took 19-38% less time than update_offsets plus
+ *     a separate contiguous copy.  CRC-64: the copy twins carry more scratch
+ *     per lane than the plain kernels; fusing saved 21% on a large batch (8192
+ *     chunks, 269 MB) but on 1024 x 64 KiB it saves the second launch, not
+ *     time (52% slower than the two passes).  DESIGN.md 4.13 has the numbers. */
+
+/* dev_out[i] = CRC(chunk i), host order, method size. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_copy_offsets(const char *hash_method, const void *dev_src,
+    const uint64_t *dev_src_offsets, void *dev_dst,
+    const uint64_t *dev_dst_starts, size_t count, void *dev_out, void *stream);
+
+/* dev_state[i] advanced over chunk i (mchecksum_gpu_state_init before,
+ * mchecksum_gpu_state_get after). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_update_copy_offsets(const char *hash_method, const void *dev_src,
+    const uint64_t *dev_src_offsets, void *dev_dst,
+    const uint64_t *dev_dst_starts, size_t count, void *dev_state,
+    void *stream);
+
 /* Batched verify of received payloads against expected values (e.g. the
  * payload hash carried in the 4-byte HG header, src/mercury_header.c:111-112,
  * after ntohl): dev_status[i] = 1 if CRC(payload i) != dev_expected[i] else 0,

@@ -1,6 +1,7 @@
 // crc_gpu_common.h -- what the CRC-32C and CRC-64 batch kernels share: payload
-// and LDS loads, the three-input XOR, result emission and mismatch counting,
-// and the byte-balanced static partition of an offsets batch.
+// and LDS loads, the three-input XOR, the copying loops' store of a piece,
+// result emission and mismatch counting, and the byte-balanced static
+// partition of an offsets batch.
 #ifndef CRC_GPU_COMMON_H
 #define CRC_GPU_COMMON_H
 
@@ -8,6 +9,7 @@
 
 #include <cstdint>
 
+#include "crc_gpu_pack_store.h"
 #include "crc_gpu_queue.h"
 #include "crc_gpu_shape.h"
 
@@ -75,6 +77,26 @@ __device__ __forceinline__ uint4 ldg16(gbyte_t p) {
     if constexpr (NT) v = __builtin_nontemporal_load(q);
     else v = *q;
     return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// The copying payload loops (COPY: mchecksum_gpu_pack_messages,
+// mchecksum_gpu_unpack_messages, and the copy kernels of crc_gpu_copy.h, both
+// widths): the lane that
+// folds a piece stores the bytes crc_gpu_pack_store.h names at dst + their
+// payload position.  A whole piece is one 16-byte store through an align-1
+// type (source and destination residues differ in general; one
+// global_store_dwordx4), an edge piece goes byte by byte.
+typedef u32x4_t piece16_t __attribute__((aligned(1)));
+typedef __attribute__((address_space(1))) uint8_t *gwbyte_t;
+__device__ __forceinline__ void store_piece(gwbyte_t dst, const PieceStore &s, const uint4 &v) {
+    if (s.whole()) {
+        *(__attribute__((address_space(1))) piece16_t *)(dst + s.lo) = u32x4_t{v.x, v.y, v.z, v.w};
+    } else {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++)
+            if (b >= s.b0 && b < s.b1) dst[s.lo + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3u)));
+    }
 }
 
 // Byte-balanced static partition of an offsets batch: wave w owns payloads

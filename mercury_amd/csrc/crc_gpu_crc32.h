@@ -12,7 +12,6 @@
 #include "crc_gpu_common.h"
 #include "crc_gpu_layout.h"
 #include "crc_gpu_mask.h"
-#include "crc_gpu_pack_store.h"
 #include "crc_gpu_queue.h"
 #include "crc_gpu_seed.h"
 #include "crc_gpu_shape.h"
@@ -172,25 +171,8 @@ __device__ void fill_lds32(uint8_t *lds, const crc32_gpu_pack_t *pk, F &&issue =
     }
 }
 
-// The copying payload loops (COPY, mchecksum_gpu_pack_messages and
-// mchecksum_gpu_unpack_messages): the lane that
-// folds a piece stores the bytes crc_gpu_pack_store.h names at dst + their
-// payload position.  A whole piece is one 16-byte store through an align-1
-// type (source and destination residues differ in general; one
-// global_store_dwordx4), an edge piece goes byte by byte.
-typedef u32x4_t piece16_t __attribute__((aligned(1)));
-typedef __attribute__((address_space(1))) uint8_t *gwbyte_t;
-__device__ __forceinline__ void store_piece(gwbyte_t dst, const PieceStore &s, const uint4 &v) {
-    if (s.whole()) {
-        *(__attribute__((address_space(1))) piece16_t *)(dst + s.lo) = u32x4_t{v.x, v.y, v.z, v.w};
-    } else {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (uint32_t b = 0; b < 16; b++)
-            if (b >= s.b0 && b < s.b1) dst[s.lo + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3u)));
-    }
-}
-
+// (The copying payload loops' store of a piece, store_piece: crc_gpu_common.h.)
+//
 // Ring slot j % kRing holds the piece of step j, loaded kRing steps ahead.
 //
 // Aligned fixed-size payload: base 16-B aligned, len = K * 16G, no masking,

@@ -306,9 +306,12 @@ __device__ __forceinline__ uint64_t payload64_aligned(const uint8_t *lds, const 
     return combine64<LOG2G, OM>(lds, pk, x0, x1, gl);
 }
 
-template <int LOG2G, bool NT, int OM = kOpsLds>
+// COPY: the payload is also stored at dst (crc_gpu_pack_store.h), as in
+// payload32_generic.
+template <int LOG2G, bool NT, int OM = kOpsLds, bool COPY = false>
 __device__ __forceinline__ uint64_t payload64_generic(const uint8_t *lds, const crc64_gpu_pack_t *pk,
-                                                      const uint8_t *p, uint64_t len, uint32_t gl, uint32_t lc) {
+                                                      const uint8_t *p, uint64_t len, uint32_t gl, uint32_t lc,
+                                                      uint8_t *dst = nullptr) {
     const uint64_t init = pk->init;
     const LaneWindow win(reinterpret_cast<uint64_t>(p), len, 8, LOG2G);
     const int64_t K = win.K, r0 = win.r0, step = win.step, hs = win.hs, he = win.he;
@@ -347,6 +350,7 @@ __device__ __forceinline__ uint64_t payload64_generic(const uint8_t *lds, const 
             const uint4 raw = ring[u];
             ring[u] = fetch(j + kRing);
             if (j < K) {
+                if constexpr (COPY) store_piece((gwbyte_t)dst, mck_lane_piece_store(win, j, win.piece(j, lane_off)), raw);
                 uint64_t w0, w1;
                 prep(j, raw, &w0, &w1);
                 x0 = f64x(lds, x0 ^ w0, 0, ln);
@@ -370,9 +374,12 @@ __device__ __forceinline__ uint64_t tail64(const uint8_t *lds, const crc64_gpu_p
 }
 
 // CRC-64 counterpart of payload32_g64 (a non-zero RAW `reg` needs len >= 8).
-template <bool NT, bool RAW = false, int OM = kOpsLds>
+// COPY: as there -- the lane that folds a piece also stores it at dst + (the
+// piece's position in the payload); dst is wave-uniform, at any alignment.
+template <bool NT, bool RAW = false, int OM = kOpsLds, bool COPY = false>
 __device__ __forceinline__ uint64_t payload64_g64(const uint8_t *lds, const crc64_gpu_pack_t *pk, const uint8_t *p,
-                                                  uint64_t len, uint32_t gl, uint32_t lc, uint64_t reg = 0ull) {
+                                                  uint64_t len, uint32_t gl, uint32_t lc, uint64_t reg = 0ull,
+                                                  uint8_t *dst = nullptr) {
     const uint64_t init = RAW ? reg : pk->init;
     const GridWindow win(reinterpret_cast<uint64_t>(p), len, 8);
     const uint32_t K = win.K, lead = win.lead;
@@ -384,7 +391,11 @@ __device__ __forceinline__ uint64_t payload64_g64(const uint8_t *lds, const crc6
 
     uint64_t x0 = 0, x1 = 0;
     Lane64 ln = lane64(lc);
+    [[maybe_unused]] gwbyte_t db = nullptr;
+    if constexpr (COPY) db = (gwbyte_t)uniform64(reinterpret_cast<uint64_t>(dst));
     auto fold = [&](uint32_t kk, uint4 v) {
+        // (the raw piece: the masking below XORs the initial register into it)
+        if constexpr (COPY) store_piece(db, mck_grid_piece_store(win, kk, gl), v);
         uint64_t w0 = lo64(v), w1 = hi64(v);
         if (kk < kc0 || kk >= kc1) {  // wave-uniform: an edge step
             const int32_t lo = (int32_t)(kk * 1024u + lo_lane) - (int32_t)qs;

@@ -1,14 +1,21 @@
 // crc_gpu_pack_store.h -- which bytes of a 16-byte piece the copying payload
-// loops (mchecksum_gpu_pack_messages: the COPY twins of the CRC-32C offsets
-// kernels) store, and where.  Shared by the HIP kernels and a CPU test
-// (tests/native/test_pack_store.c), like the edge handling (crc_gpu_mask.h)
-// and the window geometry (crc_gpu_window.h) it sits on.  Plain C++ compiles it.
+// loops store, and where: the COPY twins of the CRC-32C offsets kernels
+// (mchecksum_gpu_pack_messages, mchecksum_gpu_unpack_messages) and the copy
+// kernels of both widths (crc_gpu_copy.h: mchecksum_gpu_copy_offsets,
+// mchecksum_gpu_update_copy_offsets).  The word size -- 4 bytes for CRC-32C, 8
+// for CRC-64 -- enters only through the window geometry the caller built
+// (GridWindow(sa, len, 4 or 8), LaneWindow(sa, len, 4 or 8, log2g)): it decides
+// which pieces the loop calls clean, never which bytes are stored.  Shared by
+// the HIP kernels and two CPU tests (tests/native/test_pack_store.c for 4-byte
+// words, tests/native/test_copy_store64.cpp for 8-byte words), like the edge
+// handling (crc_gpu_mask.h) and the window geometry (crc_gpu_window.h) it sits
+// on.  Plain C++ compiles it.
 //
 // A payload loop reads whole 16-byte pieces of the window around the payload;
 // the lane that folds a piece also stores it.  For a piece whose first byte is
 // payload byte `lo` (negative before the payload, >= len past it), payload
 // byte lo + b goes to dst[lo + b] for every b with 0 <= lo + b < len -- the
-// bounds mck_mask32 clears bytes by -- and nothing else is stored: each payload
+// bounds mck_mask32 / mck_mask64 clear bytes by -- and nothing else is stored: each payload
 // byte lies in exactly one piece, so it is written exactly once, and no byte
 // outside [dst, dst + len) is written.  A piece the loop calls clean lies
 // wholly inside the payload and is stored whole; source and destination

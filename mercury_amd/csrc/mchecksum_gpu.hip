@@ -36,7 +36,9 @@
 //    the kernel for the plan and the call's operation (launch_plan.h: BatchOp,
 //    kernel_key), looks it up (kernel_for) and launches it with its
 //    work-queue slot, if the plan takes one (gpu_host.h: launch_slot).  The
-//    offsets-shaped calls share one front, offsets_call.
+//    offsets-shaped calls share one front, offsets_call.  The two
+//    copy-and-checksum calls have copy_call beside it: the same plan, pack and
+//    slot, and a kernel of the copy family (crc_gpu_copy.h, copy_plan.h).
 // No MFMA: this is HBM-bound byte scanning; the roofline is HBM read bandwidth.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +50,8 @@
 #include <mutex>
 #include <type_traits>
 
+#include "copy_plan.h"
+#include "crc_gpu_copy.h"
 #include "crc_gpu_device.h"
 #include "gpu_host.h"
 #include "launch_plan.h"
@@ -453,6 +457,93 @@ int offsets_call(const OffsetsCall &c) {
     return rc;
 }
 
+// ---- copy-and-checksum: the copy kernels (crc_gpu_copy.h) ----
+typedef void (*copy_kern_t)(CopyArgs);
+struct CopyLaunch {
+    copy_kern_t k = nullptr;
+    int block = 0;
+};
+
+// The kernel of one key, if there is one (copy_key_valid): only those are instantiated.
+template <int W, int OP, bool NT, bool LIGHT>
+CopyLaunch copy_kernel_ptr() {
+    if constexpr (copy_key_valid(CopyKey{W, OP, NT, LIGHT})) {
+        if constexpr (W == 32) return {crc32c_copy_kernel<OP, NT, LIGHT>, Shape<32, kOffsets, LIGHT>::block};
+        else return {crc64_copy_kernel<OP, NT>, Shape<64, kOffsets>::block};
+    }
+    return {};
+}
+
+// Key I of the 16 (width, op, nt, light) combinations, searched in turn: a
+// key with no kernel gives a null CopyLaunch, which copy_call reports as an
+// error and never launches.
+template <int I = 0>
+CopyLaunch copy_kernel_at(int i) {
+    if constexpr (I < 16)
+        return i == I ? copy_kernel_ptr<(I & 8) ? 64 : 32, (I >> 2) & 1, ((I >> 1) & 1) != 0, (I & 1) != 0>()
+                      : copy_kernel_at<I + 1>(i);
+    return {};
+}
+CopyLaunch copy_kernel_for(const CopyKey &k) {
+    if ((k.width != 32 && k.width != 64) || k.op < kCopyChecksum || k.op > kCopyUpdate) return {};
+    return copy_kernel_at((k.width == 64 ? 8 : 0) | k.op << 2 | (k.nt ? 2 : 0) | (k.light ? 1 : 0));
+}
+
+// One copy call, as its entry point names it: chunk i = src[src_off[i],
+// src_off[i+1]) goes to dst + dst_starts[i]; out holds the CRCs
+// (kCopyChecksum) or the running registers (kCopyUpdate).
+struct CopyCall {
+    CopyOp op;
+    const char *method;
+    const void *src;
+    const uint64_t *src_off;
+    void *dst;
+    const uint64_t *dst_starts;
+    size_t count;
+    void *out;
+    void *stream;
+};
+
+// The front of both copy entry points, beside offsets_call: its checks in
+// checksum_offsets' / update_offsets' order, and the same plan, table pack,
+// slot and launch for the same count.
+int copy_call(const CopyCall &c) {
+    // an empty batch needs no buffers
+    if (c.count && (!c.src || !c.src_off || !c.dst || !c.dst_starts || !c.out))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if ((uint64_t)c.count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    Model m;
+    int rc;
+    if ((rc = resolve_model(c.method, &m))) return rc;
+    DevCtx *dc = nullptr;
+    const void *pack = nullptr, *shift = nullptr;
+    if ((rc = device_ctx(&dc))) return rc;
+    const LaunchPlan p = plan_offsets(*mck_settings(), dc->cus, m.width, c.count);
+    if ((rc = get_pack(dc, m.idx, p.lg, &pack))) return rc;
+    if (c.op == kCopyUpdate && (rc = get_ext(dc, m.idx, &shift))) return rc;
+    if (c.count == 0) return MCHECKSUM_GPU_OK;
+    const CopyLaunch k = copy_kernel_for(copy_key(p, c.op));
+    if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no copy kernel for this call");
+    CopyArgs a{};
+    a.b.base = (const uint8_t *)c.src;
+    a.b.offsets = c.src_off;
+    a.b.count = c.count;
+    a.b.out = c.out;
+    a.b.pack = pack;
+    a.b.err_word = error_word();
+    a.b.shift = shift;
+    a.dst = (uint8_t *)c.dst;
+    a.dst_starts = c.dst_starts;
+    SlotRef sr;
+    if (p.dyn) sr = queue_slot(dc, c.stream);
+    a.b.queue = sr.q;
+    rc = launch_slot(dc, sr, k.k, p.grid, k.block, c.stream, a, "copy kernel launch");
+    // (running registers stay in the kernels' form: state_get swaps an MSB-first model's)
+    if (rc == MCHECKSUM_GPU_OK && m.msb && c.op == kCopyChecksum) rc = swap_outputs(c.out, c.count, m.width, c.stream);
+    return rc;
+}
+
 // ---- streaming state: 256-thread element kernels (grid: elem_grid) ----
 template <typename T>
 __global__ __launch_bounds__(256) void state_init_kernel(T *st, uint64_t n, T init) {
@@ -698,6 +789,21 @@ int mchecksum_gpu_update_offsets(const char *hash_method, const void *dev_base, 
     c.out = dev_state;  // advanced in place by the seeded twin of the checksum kernel the same plan picks
     c.stream = stream;
     return offsets_call(c);
+}
+
+int mchecksum_gpu_copy_offsets(const char *hash_method, const void *dev_src, const uint64_t *dev_src_offsets,
+                               void *dev_dst, const uint64_t *dev_dst_starts, size_t count, void *dev_out,
+                               void *stream) {
+    return copy_call(CopyCall{kCopyChecksum, hash_method, dev_src, dev_src_offsets, dev_dst, dev_dst_starts, count,
+                              dev_out, stream});
+}
+
+int mchecksum_gpu_update_copy_offsets(const char *hash_method, const void *dev_src, const uint64_t *dev_src_offsets,
+                                      void *dev_dst, const uint64_t *dev_dst_starts, size_t count, void *dev_state,
+                                      void *stream) {
+    // the registers are advanced in place, as update_offsets does, by the seeded twin of the same plan's copy kernel
+    return copy_call(CopyCall{kCopyUpdate, hash_method, dev_src, dev_src_offsets, dev_dst, dev_dst_starts, count,
+                              dev_state, stream});
 }
 
 int mchecksum_gpu_state_get(const char *hash_method, const void *dev_state, size_t count, void *dev_out,

@@ -224,6 +224,85 @@ def update_offsets(method: str, data: torch.Tensor, offsets: torch.Tensor, state
     return state
 
 
+def _check_copy_tables(src, dst, offsets_host, dst_starts_host):
+    """Host check of a copy call's two tables (ValueError): every destination
+    range inside dst, the ranges pairwise disjoint, and disjoint from the source
+    range -- compared by address, so a dst that shares src's storage is
+    covered.  Runs before the device checks: it needs no device."""
+    import numpy as np
+    so = np.asarray(offsets_host, dtype=np.uint64).astype(np.int64)
+    ds = np.asarray(dst_starts_host, dtype=np.uint64).astype(np.int64)
+    if so.ndim != 1 or ds.ndim != 1 or len(so) != len(ds) + 1:
+        raise ValueError("offsets_host needs one entry more than dst_starts_host")
+    if np.any(so < 0) or np.any(ds < 0) or np.any(so[1:] < so[:-1]):
+        raise ValueError("offsets must be non-decreasing")
+    lens = so[1:] - so[:-1]
+    if np.any(ds + lens > dst.numel() * dst.element_size()):
+        raise ValueError("a destination range extends past the end of dst")
+    live = lens > 0
+    lo, hi = ds[live], (ds + lens)[live]
+    order = np.argsort(lo, kind="stable")
+    lo, hi = lo[order], hi[order]
+    if np.any(hi[:-1] > lo[1:]):
+        raise ValueError("two destination ranges overlap")
+    if lo.size and src.device == dst.device:
+        s0, s1 = src.data_ptr() + int(so[0]), src.data_ptr() + int(so[-1])
+        d = dst.data_ptr()
+        if np.any((lo + d < s1) & (hi + d > s0)):
+            raise ValueError("a destination range overlaps the source range")
+
+
+def _copy_call(name, method, src, src_offsets, dst, dst_starts, out, stream, offsets_host, dst_starts_host):
+    if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor):
+        raise GpuChecksumError("src and dst must be tensors")
+    if offsets_host is not None and dst_starts_host is not None:
+        _check_copy_tables(src, dst, offsets_host, dst_starts_host)
+    _check_device_u8(src, "src")
+    _check_device_u8(dst, "dst")
+    _check_offsets(src, src_offsets, offsets_host)
+    count = src_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("src_offsets needs at least one entry")
+    if (not isinstance(dst_starts, torch.Tensor) or dst_starts.dtype != torch.int64 or not dst_starts.is_cuda
+            or not dst_starts.is_contiguous() or dst_starts.numel() != count):
+        raise GpuChecksumError("dst_starts must be a contiguous device int64 tensor of count elements")
+    _check_state(out, method, count, "out" if name == "mchecksum_gpu_copy_offsets" else "state")
+    _same_device(src, src_offsets=src_offsets, dst=dst, dst_starts=dst_starts, out=out)
+    with _on(src):
+        rc = getattr(_lib(), name)(method.encode(), src.data_ptr(), src_offsets.data_ptr(), dst.data_ptr(),
+                                   dst_starts.data_ptr(), count, out.data_ptr(), _stream_handle(stream, src.device))
+    if rc != 0:
+        _err(rc, name)
+    return out
+
+
+def copy_offsets(method: str, src: torch.Tensor, src_offsets: torch.Tensor, dst: torch.Tensor,
+                 dst_starts: torch.Tensor, out: torch.Tensor | None = None, stream=None, offsets_host=None,
+                 dst_starts_host=None) -> torch.Tensor:
+    """checksum_offsets that also copies, in one pass: chunk i = src[src_offsets[i]
+    : src_offsets[i+1]] (n_i bytes) goes to dst[dst_starts[i] : dst_starts[i] +
+    n_i] and its CRC to out[i].  dst_starts (count int64) may be in any order;
+    only those bytes of dst are written.  The destination ranges must not
+    overlap one another or the source: with both host tables given that, and
+    that every range lies inside dst, is checked here (ValueError) before any
+    launch; otherwise the tables are trusted as in the C ABI."""
+    if out is None and isinstance(src, torch.Tensor) and isinstance(src_offsets, torch.Tensor):
+        out = torch.empty(max(src_offsets.numel() - 1, 0), dtype=out_dtype(method), device=src.device)
+    return _copy_call("mchecksum_gpu_copy_offsets", method, src, src_offsets, dst, dst_starts, out, stream,
+                      offsets_host, dst_starts_host)
+
+
+def update_copy_offsets(method: str, src: torch.Tensor, src_offsets: torch.Tensor, dst: torch.Tensor,
+                        dst_starts: torch.Tensor, state: torch.Tensor, stream=None, offsets_host=None,
+                        dst_starts_host=None) -> torch.Tensor:
+    """update_offsets that also copies, in one pass: state[i] is advanced over
+    chunk i, which goes to dst[dst_starts[i] : ...] (copy_offsets' layout, rules
+    and host checks).  An empty chunk writes nothing and leaves its state
+    unchanged.  Returns state."""
+    return _copy_call("mchecksum_gpu_update_copy_offsets", method, src, src_offsets, dst, dst_starts, state, stream,
+                      offsets_host, dst_starts_host)
+
+
 def state_get(method: str, state: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
     """The CRC of every stream's bytes so far (host-order values, as the
     checksum_* calls return them).  The state is left as it is."""

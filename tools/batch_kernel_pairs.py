@@ -8,7 +8,11 @@ parameters and must leave their machine code alone.
 Each build is a directory holding what `make asm` leaves: resource_usage.txt
 and the device assembly mchecksum_gpu-hip-amdgcn-amd-amdhsa-gfx950.s.
 
-usage: batch_kernel_pairs.py OLD_DIR NEW_DIR
+usage: batch_kernel_pairs.py [--added REGEX] OLD_DIR NEW_DIR
+
+--added REGEX: functions of the new build alone whose name matches are listed
+with their resources as "added" and do not count against the pairing (a change
+that adds kernels and must leave every existing one alone).
 
 A kernel's key is read from its demangled template arguments, in either
 spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
@@ -107,11 +111,22 @@ def load(d):
 
 
 def main():
-    old, new = load(sys.argv[1]), load(sys.argv[2])
-    bad = 0
+    args = sys.argv[1:]
+    added = None  # --added REGEX: functions expected in the new build only (a change that adds kernels and must leave the rest alone)
+    if "--added" in args:
+        i = args.index("--added")
+        added = re.compile(args[i + 1])
+        del args[i:i + 2]
+    old, new = load(args[0]), load(args[1])
+    bad = nadded = 0
     print("width lanes mode operation nt light split | " + " | ".join(KEYS) + " | code bytes | instructions | stream sha1 | verdict")
     for k in sorted(set(old) | set(new)):
         label = f"{k[0]} {1 << k[1]} {k[2]} {k[3]} {k[4]} {k[5]} {k[6]}" + (f" ({k[7]}, not inlined)" if len(k) > 7 else "")
+        if added and k not in old and added.search(str(k[3])):
+            n = new[k]
+            print(f"{label} | " + " | ".join(n["res"]) + f" | {n['code']} | {n['insts']} | {n['sha']} | added")
+            nadded += 1
+            continue
         if k not in old or k not in new:
             print(f"{label} | only in the {'new' if k in new else 'old'} build")
             bad += 1
@@ -121,7 +136,8 @@ def main():
         bad += not same
         print(f"{label} | " + " | ".join(n["res"]) + f" | {n['code']} | {n['insts']} | {n['sha']} | " +
               ("same" if same else f"DIFFERS (old: {' '.join(o['res'])} | {o['code']} | {o['insts']} | {o['sha']})"))
-    print(f"{len(old)} kernels in the old build, {len(new)} in the new, {len(set(old) & set(new))} paired, {bad} differ or are unpaired")
+    print(f"{len(old)} kernels in the old build, {len(new)} in the new, {len(set(old) & set(new))} paired, "
+          + (f"{nadded} added, " if added else "") + f"{bad} differ or are unpaired")
     return 1 if bad else 0
 
 
