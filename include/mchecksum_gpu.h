@@ -373,6 +373,75 @@ mchecksum_gpu_checksum_segments(const char *hash_method,
     const uint64_t *dev_obj_first, size_t nobj, void *dev_work,
     size_t work_size, void *dev_out, void *stream);
 
+/* checksum_segments that also moves the bytes, in the same read: a bulk
+ * handle's segments linearised into one contiguous buffer (gather), or a
+ * contiguous object spread over the handle's segments (scatter).
+ *
+ * gather_segments: object j's segments, concatenated in order (N_j bytes, the
+ * sum of its segment lengths), are copied to dev_dst[dev_dst_starts[j],
+ * dev_dst_starts[j] + N_j) and hashed.  scatter_segments: object j =
+ * dev_src[dev_src_starts[j], dev_src_starts[j] + N_j) is spread over its
+ * segments in order -- dev_seg_addr are now destinations -- and hashed.
+ *
+ * Tables and limits.  The segment table, dev_obj_first, the workspace
+ * (mchecksum_gpu_segments_work_size(nseg), one per concurrent call) and the
+ * 2^40-segment cap are those of checksum_segments.  dev_dst_starts /
+ * dev_src_starts hold nobj byte offsets, in any order.  The lengths live on
+ * the device, so there is no fit rule and no status array, exactly as for
+ * mchecksum_gpu_copy_offsets.
+ *
+ * Values.  dev_out[j] equals what checksum_segments returns for the same
+ * tables, bit for bit, for every 32/64-bit catalogue method, MSB-first methods
+ * included (their outputs are swapped after the launch, as there).  An object
+ * with no bytes gets the CRC of the empty message, and nothing is written for
+ * it.
+ *
+ * Which bytes are written.  Gather writes exactly the N_j destination bytes of
+ * each object: no byte before them, after them or between objects; segment
+ * memory is never written.  Scatter writes exactly dev_seg_len[s] bytes of
+ * each segment s in [first[0], first[nobj]) and no other byte; dev_src is
+ * never written.  Segments outside [first[0], first[nobj]) are neither read
+ * nor written.  An empty segment contributes nothing.
+ *
+ * Memory and ordering.  The side that is read (each segment for gather, each
+ * object's source range for scatter) must be readable to the next 16-byte
+ * boundary after its last byte.  Written ranges must not overlap one another
+ * or anything read: the library cannot check this, because the tables are on
+ * the device, and an overlapping call copies and hashes unspecified bytes.
+ * Calls are asynchronous and stream-ordered, and capture-safe after
+ * mchecksum_gpu_prepare(): a replay scans the tables again, so lengths may
+ * change between replays, and it copies the current contents.
+ *
+ * Failure.  The calls fail closed as checksum_segments does: error word + 1
+ * once per call, and mchecksum_gpu_queue_faults().  A call whose scan gave up
+ * stores nothing.  After a failed call the outputs and the written bytes are
+ * unspecified.
+ *
+ * Arguments are checked in checksum_segments' order: NULL pointers first
+ * (dev_dst / dev_src and the starts table are required when nobj > 0), then
+ * the segment cap, then the workspace, then the device, then the method.
+ * nobj == 0 passes those checks and returns MCHECKSUM_GPU_OK.
+ *
+ * Cost.  Every chunk takes the any-alignment payload loop, also where
+ * checksum_segments would take its aligned or pipelined loop, so on lists of
+ * 16-byte aligned KiB-multiple segments the hash itself is slower than
+ * checksum_segments'; the call is meant to replace checksum_segments plus a
+ * copy per segment, not checksum_segments alone (DESIGN.md 4.14 has the
+ * measured shapes). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_gather_segments(const char *hash_method,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj,
+    void *dev_dst, const uint64_t *dev_dst_starts,
+    void *dev_work, size_t work_size, void *dev_out, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_scatter_segments(const char *hash_method,
+    const void *dev_src, const uint64_t *dev_src_starts,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj,
+    void *dev_work, size_t work_size, void *dev_out, void *stream);
+
 /* Batched check of Mercury core headers for received
  * messages in device memory: message i = dev_buf[dev_msg_offsets[i],
  * dev_msg_offsets[i+1]) starts with the 16-byte core header that

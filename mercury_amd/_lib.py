@@ -27,7 +27,8 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_queue_stats", "mchecksum_gpu_reload_settings", "mchecksum_gpu_state_init",
                "mchecksum_gpu_update_offsets", "mchecksum_gpu_state_get", "mchecksum_gpu_combine",
                "mchecksum_gpu_seal_messages", "mchecksum_gpu_pack_messages", "mchecksum_gpu_seal_core_headers",
-               "mchecksum_gpu_unpack_messages", "mchecksum_gpu_copy_offsets", "mchecksum_gpu_update_copy_offsets")
+               "mchecksum_gpu_unpack_messages", "mchecksum_gpu_copy_offsets", "mchecksum_gpu_update_copy_offsets",
+               "mchecksum_gpu_gather_segments", "mchecksum_gpu_scatter_segments")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
@@ -83,6 +84,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_checksum_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                                   c_void_p, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_checksum_segments.restype = c_int
+    # (method, seg_addr, seg_len, nseg, obj_first, nobj, dst, dst_starts, work, work_size, out, stream)
+    L.mchecksum_gpu_gather_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.mchecksum_gpu_gather_segments.restype = c_int
+    # (method, src, src_starts, seg_addr, seg_len, nseg, obj_first, nobj, work, work_size, out, stream)
+    L.mchecksum_gpu_scatter_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                                 c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.mchecksum_gpu_scatter_segments.restype = c_int
     L.mchecksum_gpu_verify_core_headers.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                                     c_void_p, c_void_p]
     L.mchecksum_gpu_verify_core_headers.restype = c_int

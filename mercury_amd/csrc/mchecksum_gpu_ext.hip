@@ -32,6 +32,7 @@
 #include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
+#include "seg_copy_plan.h"
 
 namespace {
 
@@ -60,6 +61,7 @@ namespace {
 // segment, while the shift (a few us of dependent scalar loads) stays a few
 // percent of a chunk's scan time.  A chunk that ends its object needs no shift.
 constexpr uint64_t kChunk = 256u << 10;
+static_assert(kChunk == mck::kSegChunk, "seg_copy_plan.h cuts segments as the chunk passes do");
 
 struct SegArgs {
     const uint64_t *addr, *len;
@@ -478,7 +480,7 @@ struct ChunkWalk {
     const SegArgs *a;
     uint64_t c, c1, s, j;
 
-    __device__ ChunkWalk(const SegArgs &args, uint32_t wave, uint32_t nw, uint64_t nchunks) : a(&args) {
+    __device__ __forceinline__ ChunkWalk(const SegArgs &args, uint32_t wave, uint32_t nw, uint64_t nchunks) : a(&args) {
         c = nchunks * wave / nw;
         c1 = nchunks * (wave + 1) / nw;
         s = c < c1 ? lower_bound_u64(a->C, a->nseg + 1, c + 1) - 1 : 0;
@@ -488,7 +490,7 @@ struct ChunkWalk {
     // Next chunk: its bytes [addr, addr + n) and, when its segment belongs to
     // an object (*in), the object, the object bytes that follow it (*end -
     // *stop, as seg_locate) and whether it starts the object (*head).
-    __device__ bool next(uint64_t *addr, uint64_t *n, bool *in, uint64_t *obj, uint64_t *end, uint64_t *stop,
+    __device__ __forceinline__ bool next(uint64_t *addr, uint64_t *n, bool *in, uint64_t *obj, uint64_t *end, uint64_t *stop,
                          bool *head) {
         if (c >= c1) return false;
         while (s < a->nseg && a->C[s + 1] <= c) s++;  // skips empty segments
@@ -569,6 +571,13 @@ __device__ __forceinline__ void seg_locate(const SegArgs &a, uint64_t c, uint64_
         const uint64_t hs = o4[3];
         *head = hs != kNoObj ? hs == s && off == 0 : at == a.P[o4[1]];
     }
+}
+// The first segment of the object of chunk c, which seg_locate placed in an
+// object (the copying pass: the chunk's place in its object counts from
+// there): seg_locate's segment again, then the second word of its record.
+__device__ __forceinline__ uint64_t seg_locate_first(const SegArgs &a, uint64_t c, uint64_t nchunks) {
+    const uint64_t s = nchunks <= a.map_cap ? (uint64_t)a.map[c] : lower_bound_u64(a.C, a.nseg + 1, c + 1) - 1;
+    return a.obj[4 * s + 1];
 }
 
 // The chunk passes, one launch after the scan: one 1024-thread workgroup per
@@ -715,6 +724,107 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
             have = next;
         }
         const bool faulted = tk.finish(wave);
+        if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
+    }
+}
+
+// The copying chunk passes (mchecksum_gpu_gather_segments, _scatter_segments):
+// seg_kernel's walk, head-chunk rule, shift and output XOR, with every chunk
+// also stored on the other side by the payload loop that hashes it, so each
+// byte is read once.  DIR (seg_copy_plan.h): gather loads the chunk from its
+// segment and stores it at its place in the object's contiguous range,
+// scatter the reverse; the hashed bytes are the loaded ones either way.  The
+// chunk's place in its object is P[s] + off - P[first[j]]: one more scalar
+// load than seg_kernel per chunk (the queue pass has first[j] in the
+// segment's record).  Every chunk takes the one-payload-per-wave loop in its
+// RAW, COPY form (chunks are at most 256 KiB): right for every alignment of
+// either side, and the store rule (crc_gpu_pack_store.h) writes only the
+// chunk's own bytes -- whole 16-byte pieces unaligned, edge pieces byte by
+// byte -- so the waves that store neighbouring chunks of one object never
+// touch the same byte and nothing is read back from the destination.  The
+// aligned loops have no COPY form, and the CRC-64 pass is not pipelined
+// across chunks.
+struct SegCopyArgs {
+    SegArgs s;
+    uint8_t *flat;           // the contiguous side: gather's destination, scatter's source
+    const uint64_t *starts;  // nobj byte offsets into it
+};
+
+template <int W, int DIR>
+__global__ __launch_bounds__(1024, 1) void seg_copy_kernel(SegCopyArgs ca) {
+    static_assert(DIR == mck::kSegGather || DIR == mck::kSegScatter, "no such direction");
+    const SegArgs &a = ca.s;
+    __shared__ __attribute__((aligned(16))) uint8_t lds_tab[W == 32 ? kL32Bytes : kL64Bytes];
+    constexpr int kWPB = 1024 / 64;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWPB + (threadIdx.x >> 6));
+    const uint32_t nw = gridDim.x * kWPB;
+    const uint64_t nchunks = uniform(a.C[a.nseg]);
+    __shared__ WgQueue wgq;
+    if (W == 64 && threadIdx.x == 0) wg_queue_init(&wgq, a.queue, nchunks);
+    // the scan of this call gave up (reported on the error word): hash nothing
+    // and, ahead of the first store below, write nothing
+    if (uniform(ld_relaxed(a.fault_claim)) == scan_key(a.epoch, uniform(ld_relaxed(a.gen)) - 1)) return;
+    const bool nt = uniform(a.P[a.nseg]) >= kSegNtBytes;  // as seg_kernel
+    const uint64_t flat = reinterpret_cast<uint64_t>(ca.flat);
+    if constexpr (W == 32) {
+        uint8_t *lds_raw = lds_tab;
+        const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
+        const crc32_shift_pack_t *sp = reinterpret_cast<const crc32_shift_pack_t *>(a.shift);
+        [[clang::always_inline]] fill_lds32<false, 1024>(lds_raw, pk);  // (as it is in seg_kernel)
+        __syncthreads();
+        const Tab32<false> lds{lds_raw};
+        const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
+        uint32_t *out = reinterpret_cast<uint32_t *>(a.out);
+        const uint32_t init = pk->init;
+        ChunkWalk walk(a, wave, nw, nchunks);
+        uint64_t p, n, j = 0, end = 0, stop = 0;
+        bool in, head = false;
+        while (walk.next(&p, &n, &in, &j, &end, &stop, &head)) {
+            if (!in) continue;
+            const uint64_t at = stop - n, obj_at = a.P[a.first[j]];
+            if (at < obj_at) continue;  // an untrusted scan, as stop > end in the walk: no store anywhere
+            const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, p, flat, ca.starts[j], at, obj_at);
+            const uint8_t *q = reinterpret_cast<const uint8_t *>(ad.load);
+            uint8_t *d = reinterpret_cast<uint8_t *>(ad.store);
+            const uint32_t reg = head && n >= 4 ? init : 0u;
+            uint32_t x = nt ? payload32_g64<true, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d)
+                            : payload32_g64<false, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d);
+            x = uniform(x);
+            if (head && n < 4) x ^= pk->zinit[n];
+            x = shift32(sp, x, end - stop);
+            if (lane == 0) atomicXor(out + j, head ? x ^ init : x);
+        }
+    } else {
+        uint8_t *lds = lds_tab;
+        const crc64_gpu_pack_t *pk = reinterpret_cast<const crc64_gpu_pack_t *>(a.pack);
+        const crc64_shift_pack_t *sp = reinterpret_cast<const crc64_shift_pack_t *>(a.shift);
+        fill_lds64<1024, kOpsLds, /*USER*/ 1>(lds, pk);  // (an instantiation of its own: crc_gpu_crc64.h)
+        __syncthreads();
+        const uint32_t lc = (lane & 31u) << 3;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(a.out);
+        const uint64_t init = pk->init;
+        auto one = [&](uint64_t c) {
+            uint64_t p = 0, n = 0, j = 0, end = 0, stop = 0;
+            bool in = false, head = false;
+            seg_locate(a, c, nchunks, &p, &n, &in, &j, &end, &stop, &head);
+            if (!in || stop > end) return;  // (an untrusted scan, as seg_kernel)
+            const uint64_t fs = seg_locate_first(a, c, nchunks);
+            if (fs > a.nseg) return;
+            const uint64_t at = stop - n, obj_at = a.P[fs];
+            if (at < obj_at) return;
+            const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, p, flat, ca.starts[j], at, obj_at);
+            const uint8_t *q = reinterpret_cast<const uint8_t *>(ad.load);
+            uint8_t *d = reinterpret_cast<uint8_t *>(ad.store);
+            const uint64_t reg = head && n >= 8 ? init : 0ull;
+            uint64_t x = nt ? payload64_g64<true, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d)
+                            : payload64_g64<false, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d);
+            x = uniform(x);
+            if (head && n < 8) x ^= pk->zinit[n];
+            x = shift64(sp, x, end - stop);
+            if (lane == 0) atomicXor(out + j, (unsigned long long)(head ? x ^ init : x));
+        };
+        const bool faulted = for_each_unit<true>(&wgq, a.queue, nchunks, wave, nw, one);
         if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
     }
 }
@@ -1104,10 +1214,18 @@ size_t mchecksum_gpu_segments_work_size(size_t nseg) {
     return sizeof(uint64_t) * seg_words(nseg) + sizeof(uint32_t) * seg_map_cap(nseg);
 }
 
-int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev_seg_addr,
-                                    const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
-                                    size_t nobj, void *dev_work, size_t work_size, void *dev_out, void *stream) {
-    if (!dev_obj_first || (nobj && !dev_out) || (nseg && (!dev_seg_addr || !dev_seg_len)) || !dev_work)
+// checksum_segments, gather_segments and scatter_segments: the argument
+// checks, the scan launch and the chunk pass -- seg_kernel, or for a copying
+// call (dir = mck::kSegGather / kSegScatter, with the contiguous side dev_flat
+// and its dev_starts table) seg_copy_kernel under the same launch policy.
+constexpr int kSegHashOnly = -1;
+static int seg_copy_call(const char *hash_method, int dir, void *dev_flat, const uint64_t *dev_starts,
+                         const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+                         const uint64_t *dev_obj_first, size_t nobj, void *dev_work, size_t work_size, void *dev_out,
+                         void *stream) {
+    const bool copy = dir != kSegHashOnly;
+    if (!dev_obj_first || (nobj && !dev_out) || (nseg && (!dev_seg_addr || !dev_seg_len)) || !dev_work ||
+        (copy && nobj && (!dev_flat || !dev_starts)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if ((uint64_t)nseg > kMaxSegs) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^40 segments in one call");
     if (work_size < mchecksum_gpu_segments_work_size(nseg) || (uintptr_t)dev_work % 8)
@@ -1181,11 +1299,42 @@ int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev
     SlotRef sr;  // only the CRC-64 pass takes chunks from a work queue
     if (width == 64) sr = queue_slot(c, stream);
     a.queue = sr.q;
-    rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, stream, a,
-                     "segment kernel launch");
+    if (!copy) {
+        rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, stream, a,
+                         "segment kernel launch");
+    } else {
+        const SegCopyArgs ca{a, (uint8_t *)dev_flat, dev_starts};
+        const bool gather = dir == mck::kSegGather;
+        auto k = width == 32 ? (gather ? seg_copy_kernel<32, mck::kSegGather> : seg_copy_kernel<32, mck::kSegScatter>)
+                             : (gather ? seg_copy_kernel<64, mck::kSegGather> : seg_copy_kernel<64, mck::kSegScatter>);
+        rc = launch_slot(c, sr, k, (unsigned)c->cus, 1024, stream, ca, "segment copy kernel launch");
+    }
     // MSB-first model: the kernels' values are the CRCs byte-swapped (crc_gpu_layout.h)
     if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(dev_out, nobj, width, stream);
     return rc;
+}
+
+int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev_seg_addr,
+                                    const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
+                                    size_t nobj, void *dev_work, size_t work_size, void *dev_out, void *stream) {
+    return seg_copy_call(hash_method, kSegHashOnly, nullptr, nullptr, dev_seg_addr, dev_seg_len, nseg, dev_obj_first,
+                         nobj, dev_work, work_size, dev_out, stream);
+}
+
+int mchecksum_gpu_gather_segments(const char *hash_method, const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len,
+                                  size_t nseg, const uint64_t *dev_obj_first, size_t nobj, void *dev_dst,
+                                  const uint64_t *dev_dst_starts, void *dev_work, size_t work_size, void *dev_out,
+                                  void *stream) {
+    return seg_copy_call(hash_method, mck::kSegGather, dev_dst, dev_dst_starts, dev_seg_addr, dev_seg_len, nseg,
+                         dev_obj_first, nobj, dev_work, work_size, dev_out, stream);
+}
+
+int mchecksum_gpu_scatter_segments(const char *hash_method, const void *dev_src, const uint64_t *dev_src_starts,
+                                   const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+                                   const uint64_t *dev_obj_first, size_t nobj, void *dev_work, size_t work_size,
+                                   void *dev_out, void *stream) {
+    return seg_copy_call(hash_method, mck::kSegScatter, const_cast<void *>(dev_src), dev_src_starts, dev_seg_addr,
+                         dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_out, stream);
 }
 
 // verify_core_headers and seal_core_headers: the argument checks, the 16-bit

@@ -554,11 +554,15 @@ class SegmentBatch:
         self.device = dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
         self.bytes = int(np.sum(np.asarray(lens, dtype=np.int64)[first[0]:first[-1]])) if self.nseg else 0
         self._cap = np.asarray(lens, dtype=np.int64)  # each segment's size as given: set_lengths stays within it
+        self._addr = np.asarray(addr, dtype=np.uint64)  # host copies of the tables, for gather's / scatter's checks:
+        self._lens = self._cap.copy()                    # the current lengths (set_lengths keeps them) ...
+        self._first = first.copy()                       # ... and the objects' first segments
         self._span = (int(first[0]), int(first[-1]))
         self.meta = torch.from_numpy(np.concatenate([np.asarray(addr, dtype=np.uint64).view(np.int64),
                                                      np.asarray(lens, dtype=np.int64), first])).to(self.device)
         self.work = torch.empty((_lib().mchecksum_gpu_segments_work_size(self.nseg) + 7) // 8, dtype=torch.int64,
                                 device=self.device)
+        self._starts = None  # the starts table of the last gather / scatter: alive for a captured call's replays
         self._last = None  # (stream handle, its torch stream, event after the call or None) of the last call
 
     def set_lengths(self, lens, stream=None) -> None:
@@ -580,16 +584,21 @@ class SegmentBatch:
             if torch.cuda.is_current_stream_capturing():
                 raise GpuChecksumError("set_lengths during graph capture: the copy would bake these lengths in")
             self.meta[self.nseg:2 * self.nseg].copy_(torch.from_numpy(lens))
+        self._lens = lens.copy()
         self.bytes = int(np.sum(lens[self._span[0]:self._span[1]])) if self.nseg else 0
 
-    def checksum(self, method: str, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    def _out(self, method: str, out):
         if out is None:
             out = torch.empty(self.nobj, dtype=out_dtype(method), device=self.device)
         elif out.numel() < self.nobj or out.dtype != out_dtype(method) or not out.is_cuda or not out.is_contiguous():
             raise GpuChecksumError("out tensor has the wrong size, dtype or device, or is not contiguous")
         if out.device != self.device:
             raise GpuChecksumError(f"out must be on {self.device}")
-        base, n = self.meta.data_ptr(), self.nseg
+        return out
+
+    def _run(self, name: str, stream, call) -> None:
+        """One C-ABI call on the batch's workspace: call(stream handle) -> rc,
+        ordered after the previous call's use of the workspace."""
         with torch.cuda.device(self.device):
             h = _stream_handle(stream, self.device)
             # (graph capture: replays are ordered by the graph's user; no events)
@@ -609,9 +618,7 @@ class SegmentBatch:
                     ev = torch.cuda.Event()
                     ev.record(self._last[1])
                 s.wait_event(ev)
-            rc = _lib().mchecksum_gpu_checksum_segments(method.encode(), base, base + 8 * n, n, base + 16 * n,
-                                                        self.nobj, self.work.data_ptr(), self.work.numel() * 8,
-                                                        out.data_ptr(), h)
+            rc = call(h)
             if rc == 0 and track:
                 ev = None
                 if not _torch_owned(stream, h, self.device):
@@ -619,15 +626,121 @@ class SegmentBatch:
                     ev.record(s)
                 self._last = (h, s, ev)
         if rc != 0:
-            _err(rc, "mchecksum_gpu_checksum_segments")
+            _err(rc, name)
+
+    def checksum(self, method: str, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        out = self._out(method, out)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_checksum_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_checksum_segments(method.encode(), base, base + 8 * n, n,
+                                                                   base + 16 * n, self.nobj, self.work.data_ptr(),
+                                                                   self.work.numel() * 8, out.data_ptr(), h))
+        return out
+
+    def _flat(self, flat, starts, starts_host, what: str):
+        """Checks of gather's dst / scatter's src and its starts table; returns
+        the device starts tensor.  The host check of the tables comes first
+        (ValueError, no device needed): of a host sequence, or of starts_host
+        beside a device tensor, which is otherwise trusted as in the C ABI."""
+        import numpy as np
+        if not isinstance(flat, torch.Tensor):
+            raise GpuChecksumError(f"{what} must be a tensor")
+        sh = starts_host if isinstance(starts, torch.Tensor) else np.asarray(starts)
+        if sh is not None:
+            _check_segment_tables(flat.numel() * flat.element_size(), flat.data_ptr(), sh, self._addr, self._lens,
+                                  self._first)
+        _check_device_u8(flat, what)
+        if flat.device != self.device:
+            raise GpuChecksumError(f"{what} must be on {self.device}")
+        if isinstance(starts, torch.Tensor):
+            if (starts.dtype != torch.int64 or starts.device != self.device or not starts.is_contiguous()
+                    or starts.numel() != self.nobj):
+                raise GpuChecksumError(f"{what}_starts must be a contiguous int64 tensor of nobj elements on "
+                                       f"{self.device}")
+            return starts
+        return torch.from_numpy(np.ascontiguousarray(sh, dtype=np.uint64).view(np.int64)).to(self.device)
+
+    def gather(self, method: str, dst: torch.Tensor, dst_starts, out: torch.Tensor | None = None,
+               stream=None, dst_starts_host=None) -> torch.Tensor:
+        """checksum that also linearises, in one pass: object j's segments, in
+        order, go to dst[dst_starts[j] : dst_starts[j] + N_j] (N_j = the sum
+        of its current segment lengths) and its CRC to out[j].  dst_starts:
+        nobj byte offsets in any order -- a host sequence, uploaded here, or a
+        device int64 tensor (for a call captured into a graph, and to reuse
+        one table).  Only those bytes of dst are written.  A host sequence, or
+        dst_starts_host beside a device tensor, is checked before any launch
+        (ValueError): every range inside dst, the ranges disjoint from one
+        another and from every segment; a device tensor alone is trusted, as
+        in the C ABI."""
+        st = self._flat(dst, dst_starts, dst_starts_host, "dst")
+        out = self._out(method, out)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_gather_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_gather_segments(method.encode(), base, base + 8 * n, n, base + 16 * n,
+                                                                 self.nobj, dst.data_ptr(), st.data_ptr(),
+                                                                 self.work.data_ptr(), self.work.numel() * 8,
+                                                                 out.data_ptr(), h))
+        self._starts = st  # (kept alive for a captured call's replays)
+        return out
+
+    def scatter(self, method: str, src: torch.Tensor, src_starts, out: torch.Tensor | None = None,
+                stream=None, src_starts_host=None) -> torch.Tensor:
+        """The reverse of gather: object j = src[src_starts[j] : src_starts[j]
+        + N_j] is spread over its segments in order -- the segment tensors are
+        written, exactly their current lengths -- and its CRC goes to out[j].
+        gather's rules for src_starts and its host checks."""
+        st = self._flat(src, src_starts, src_starts_host, "src")
+        out = self._out(method, out)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_scatter_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_scatter_segments(method.encode(), src.data_ptr(), st.data_ptr(), base,
+                                                                  base + 8 * n, n, base + 16 * n, self.nobj,
+                                                                  self.work.data_ptr(), self.work.numel() * 8,
+                                                                  out.data_ptr(), h))
+        self._starts = st
         return out
 
 
-def checksum_segments(method: str, segments, obj_first=None, out: torch.Tensor | None = None,
-                      stream=None) -> torch.Tensor:
-    """One-shot SegmentBatch(segments, obj_first).checksum(method)."""
-    b = SegmentBatch(segments, obj_first)
-    out = b.checksum(method, out, stream)
+def _check_segment_tables(flat_bytes: int, flat_addr: int, starts, seg_addr, seg_lens, first) -> None:
+    """Host check of a gather / scatter call (ValueError), callable without a
+    device: `starts` has one entry per object; object j's range [starts[j],
+    starts[j] + N_j) -- N_j the sum of seg_lens over [first[j], first[j+1]) --
+    lies inside the contiguous tensor of flat_bytes bytes at address
+    flat_addr; the ranges of two objects do not overlap; and no range overlaps
+    a segment of [first[0], first[-1]), compared by address, so a contiguous
+    tensor that shares the segments' storage is covered.  Empty objects and
+    empty segments are no ranges."""
+    import numpy as np
+    first = np.asarray(first, dtype=np.int64)
+    lens = np.asarray(seg_lens, dtype=np.int64)
+    addr = np.asarray(seg_addr, dtype=np.uint64).astype(np.int64)
+    starts = np.asarray(starts)
+    nobj = len(first) - 1
+    if starts.ndim != 1 or len(starts) != nobj:
+        raise ValueError(f"the starts table needs {nobj} entries, one per object")
+    starts = starts.astype(np.uint64).astype(np.int64) if nobj else np.zeros(0, dtype=np.int64)
+    if np.any(starts < 0):
+        raise ValueError("a start is negative")
+    P = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    n = P[first[1:]] - P[first[:-1]]
+    live = n > 0
+    if np.any((starts + n)[live] > flat_bytes):
+        raise ValueError("an object's range extends past the end of the contiguous tensor")
+    lo, hi = starts[live], (starts + n)[live]
+    order = np.argsort(lo, kind="stable")
+    lo, hi = lo[order], hi[order]
+    if np.any(hi[:-1] > lo[1:]):
+        raise ValueError("two objects' ranges overlap")
+    if lo.size:
+        sl = slice(int(first[0]), int(first[-1]))
+        s0, s1 = addr[sl][lens[sl] > 0], (addr[sl] + lens[sl])[lens[sl] > 0]
+        a, b = lo + flat_addr, hi + flat_addr  # sorted, disjoint: a segment overlaps one iff it does its neighbours
+        i = np.searchsorted(b, s0, side="right")  # first range that ends after the segment's start
+        if np.any((i < a.size) & (a[np.minimum(i, a.size - 1)] < s1)):
+            raise ValueError("an object's range overlaps a segment")
+
+
+def _after_one_shot(b, stream):
     # the batch's device table and workspace are freed on return: the caching
     # allocator orders their reuse after this launch on the current stream;
     # another stream must be recorded
@@ -635,8 +748,36 @@ def checksum_segments(method: str, segments, obj_first=None, out: torch.Tensor |
         if isinstance(stream, torch.cuda.Stream):
             b.meta.record_stream(stream)
             b.work.record_stream(stream)
+            if b._starts is not None:
+                b._starts.record_stream(stream)
         else:
             torch.cuda.synchronize(b.device)
+
+
+def gather_segments(method: str, segments, dst: torch.Tensor, dst_starts, obj_first=None,
+                    out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """One-shot SegmentBatch(segments, obj_first).gather(method, dst, dst_starts)."""
+    b = SegmentBatch(segments, obj_first)
+    out = b.gather(method, dst, dst_starts, out, stream)
+    _after_one_shot(b, stream)
+    return out
+
+
+def scatter_segments(method: str, src: torch.Tensor, src_starts, segments, obj_first=None,
+                     out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """One-shot SegmentBatch(segments, obj_first).scatter(method, src, src_starts)."""
+    b = SegmentBatch(segments, obj_first)
+    out = b.scatter(method, src, src_starts, out, stream)
+    _after_one_shot(b, stream)
+    return out
+
+
+def checksum_segments(method: str, segments, obj_first=None, out: torch.Tensor | None = None,
+                      stream=None) -> torch.Tensor:
+    """One-shot SegmentBatch(segments, obj_first).checksum(method)."""
+    b = SegmentBatch(segments, obj_first)
+    out = b.checksum(method, out, stream)
+    _after_one_shot(b, stream)
     return out
 
 

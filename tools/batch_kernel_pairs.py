@@ -8,11 +8,15 @@ parameters and must leave their machine code alone.
 Each build is a directory holding what `make asm` leaves: resource_usage.txt
 and the device assembly mchecksum_gpu-hip-amdgcn-amd-amdhsa-gfx950.s.
 
-usage: batch_kernel_pairs.py [--added REGEX] OLD_DIR NEW_DIR
+usage: batch_kernel_pairs.py [--added REGEX] [--asm FILE] OLD_DIR NEW_DIR
 
 --added REGEX: functions of the new build alone whose name matches are listed
 with their resources as "added" and do not count against the pairing (a change
 that adds kernels and must leave every existing one alone).
+
+--asm FILE: the device assembly's file name in both directories, for a build
+of another source file (mchecksum_gpu_ext-hip-amdgcn-amd-amdhsa-gfx950.s: the
+segment, core-header and XDR kernels, all paired by name).
 
 A kernel's key is read from its demangled template arguments, in either
 spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
@@ -89,9 +93,9 @@ def streams(path):
     return out
 
 
-def load(d):
+def load(d, asm_name=ASM):
     res = parse(os.path.join(d, "resource_usage.txt"))  # keyed by demangled name
-    asm = streams(os.path.join(d, ASM))
+    asm = streams(os.path.join(d, asm_name))
     names = demangle(list(asm))
     rows = {}
     for mangled, (sha, n, size) in asm.items():
@@ -117,7 +121,12 @@ def main():
         i = args.index("--added")
         added = re.compile(args[i + 1])
         del args[i:i + 2]
-    old, new = load(args[0]), load(args[1])
+    asm_name = ASM
+    if "--asm" in args:
+        i = args.index("--asm")
+        asm_name = args[i + 1]
+        del args[i:i + 2]
+    old, new = load(args[0], asm_name), load(args[1], asm_name)
     bad = nadded = 0
     print("width lanes mode operation nt light split | " + " | ".join(KEYS) + " | code bytes | instructions | stream sha1 | verdict")
     for k in sorted(set(old) | set(new)):
