@@ -177,11 +177,64 @@ mchecksum_gpu_state_get(const char *hash_method, const void *dev_state,
  * CRC(B_i) -- finalized values as the checksum_* calls and state_get return
  * them -- and dev_len_b[i] = the bytes of B_i (< 2^48).  For chunks that
  * complete out of order: hash each on its own, join afterwards, left to
- * right.  dev_out may alias dev_crc_a or dev_crc_b. */
+ * right (all of an object's chunks in one launch:
+ * mchecksum_gpu_combine_runs).  dev_out may alias dev_crc_a or dev_crc_b. */
 MCHECKSUM_PUBLIC int
 mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a,
     const void *dev_crc_b, const uint64_t *dev_len_b, size_t count,
     void *dev_out, void *stream);
+
+/* The last step of a pipelined transfer, in one call: the CRCs of each
+ * object's chunks, which completed in any order, joined into the object's CRC.
+ * Also the per-object CRC from per-block CRCs (checksum_fixed over the blocks)
+ * without reading the data again.
+ *
+ * Chunk k has the finalized CRC dev_crc[k] (host order, method size: what the
+ * checksum_* / copy_offsets calls and state_get return) and dev_len[k] bytes.
+ * dev_run_first holds nruns + 1 non-decreasing indices <= nchunks (the shape
+ * of checksum_segments' dev_obj_first); run j is chunks [dev_run_first[j],
+ * dev_run_first[j+1]), in that order.
+ *
+ *   - dev_out[j] = what mchecksum_get() returns after hashing the run's chunks
+ *     concatenated in order (nruns host-order values of the method's size).
+ *   - dev_out_len[j] (optional: may be NULL) = the run's byte total.  With it a
+ *     call's outputs are valid chunk inputs of a further call: join a very
+ *     long run in two levels (runs of about a thousand chunks, then one run
+ *     over the results), or join partial joins as more chunks arrive.
+ *   - An empty run gets the CRC of the empty message and length 0.  A chunk
+ *     with dev_len[k] == 0 contributes nothing, whatever dev_crc[k] holds.
+ *     Chunks outside [first[0], first[nruns]) are not read.
+ *   - Every 32/64-bit catalogue method, MSB-first ones included; values go in
+ *     and come out in the checksum calls' form (no swap launch follows).
+ *     16-bit methods return MCHECKSUM_GPU_EMETHOD.
+ *   - A run's byte total must be < 2^48, the shift pack's range, as in
+ *     mchecksum_gpu_combine (beyond it the value is unspecified; nothing is
+ *     read out of range).  nchunks and nruns are at most 2^31 each.
+ *   - Arguments are checked in combine's order: NULL pointers and the caps
+ *     (MCHECKSUM_GPU_EINVAL), then the device, then the method.  dev_run_first
+ *     and dev_out are required when nruns > 0, dev_crc and dev_len when
+ *     nchunks > 0.  nruns == 0 passes those checks and returns
+ *     MCHECKSUM_GPU_OK without a launch; nchunks == 0 with nruns > 0 is legal
+ *     (every run is empty).
+ *   - dev_out and dev_out_len must not overlap dev_crc, dev_len or
+ *     dev_run_first: runs are joined in parallel, and one run's output would
+ *     land in a table another is still reading.
+ *   - Asynchronous and stream-ordered; capture-safe after
+ *     mchecksum_gpu_prepare().  A replay reads all three tables again, so
+ *     CRCs, lengths and run boundaries may change between replays.
+ *   - The kernel has no device-side wait, takes no work-queue slot and needs
+ *     no workspace: there is nothing to fail closed on, and the call adds
+ *     nothing to the error word or to mchecksum_gpu_queue_faults().
+ *   - One launch whatever the run sizes: a wave per run, the whole workgroup
+ *     for a run of more than 4096 chunks.  One very long run is one
+ *     workgroup's work -- correct, but slow (2^20 chunks: 7 ms crc32c, 29 ms
+ *     crc64); join it in two levels through dev_out_len (runs of 1024, then
+ *     one run of 1024: 0.09 and 0.14 ms).  DESIGN.md 4.15 has the numbers. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_combine_runs(const char *hash_method,
+    const void *dev_crc, const uint64_t *dev_len, size_t nchunks,
+    const uint64_t *dev_run_first, size_t nruns,
+    void *dev_out, uint64_t *dev_out_len, void *stream);
 
 /* Copy and checksum in one pass: many device-resident chunks are copied to
  * independent destinations and hashed in the same read -- a chunk of a bulk

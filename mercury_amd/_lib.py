@@ -28,7 +28,7 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_update_offsets", "mchecksum_gpu_state_get", "mchecksum_gpu_combine",
                "mchecksum_gpu_seal_messages", "mchecksum_gpu_pack_messages", "mchecksum_gpu_seal_core_headers",
                "mchecksum_gpu_unpack_messages", "mchecksum_gpu_copy_offsets", "mchecksum_gpu_update_copy_offsets",
-               "mchecksum_gpu_gather_segments", "mchecksum_gpu_scatter_segments")
+               "mchecksum_gpu_gather_segments", "mchecksum_gpu_scatter_segments", "mchecksum_gpu_combine_runs")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
@@ -114,6 +114,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_state_get.restype = c_int
     L.mchecksum_gpu_combine.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_combine.restype = c_int
+    # (method, crc, len, nchunks, run_first, nruns, out, out_len, stream)
+    L.mchecksum_gpu_combine_runs.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                             c_void_p, c_void_p]
+    L.mchecksum_gpu_combine_runs.restype = c_int
     L.mchecksum_gpu_seal_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p,
                                               c_void_p]
     L.mchecksum_gpu_seal_messages.restype = c_int

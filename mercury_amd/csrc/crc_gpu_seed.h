@@ -1,8 +1,9 @@
 /*
  * crc_gpu_seed.h -- the algebra of the streaming batch calls
- * (mchecksum_gpu_state_init / update_offsets / state_get / combine), shared
- * verbatim by the HIP kernels and the CPU test tests/native/test_seed_update.c
- * so the CPU checks the exact code the GPU runs.
+ * (mchecksum_gpu_state_init / update_offsets / state_get / combine /
+ * combine_runs), shared verbatim by the HIP kernels and the CPU tests
+ * tests/native/test_seed_update.c and test_join_runs.c so the CPU checks the
+ * exact code the GPU runs.
  *
  * R(s, M) is the register after hashing the n bytes of M starting from
  * register s (crc_gpu_layout.h: reflected form; an MSB-first model in its
@@ -119,6 +120,75 @@ mck_combine64(const crc64_shift_pack_t *sp, uint64_t a, uint64_t b, uint64_t len
 {
     const uint64_t ra = mck_crc_to_reg64(a, xorout, msb), rb = mck_crc_to_reg64(b, xorout, msb);
     return mck_reg_to_crc64(mck_seed64(sp, rb, ra, init, len_b), xorout, msb);
+}
+
+/* The join of mchecksum_gpu_combine_runs: the monoid of (r, n) = (R(init, M),
+ * |M|) under concatenation.
+ *
+ *     identity   (init, 0)                          the empty message
+ *     a o b    = (mck_seed(b.r, a.r, init, b.n), a.n + b.n)        A || B
+ *
+ * Associative (concatenation is), not commutative: a reduction may bracket
+ * the chunks of a run any way it likes as long as it keeps them in order.
+ * join_in maps a finalized CRC and its byte count to an element -- a
+ * zero-length chunk to the identity, whatever its CRC word holds --, join_out
+ * an element back to the finalized CRC. */
+typedef struct {
+    uint32_t r;
+    uint64_t n;
+} mck_join32_t;
+
+typedef struct {
+    uint64_t r;
+    uint64_t n;
+} mck_join64_t;
+
+MCK_HD mck_join32_t
+mck_join_in32(uint32_t v, uint64_t n, uint32_t init, uint32_t xorout, int msb)
+{
+    mck_join32_t e;
+    e.r = n ? mck_crc_to_reg32(v, xorout, msb) : init;
+    e.n = n;
+    return e;
+}
+
+MCK_HD mck_join64_t
+mck_join_in64(uint64_t v, uint64_t n, uint64_t init, uint64_t xorout, int msb)
+{
+    mck_join64_t e;
+    e.r = n ? mck_crc_to_reg64(v, xorout, msb) : init;
+    e.n = n;
+    return e;
+}
+
+MCK_HD mck_join32_t
+mck_join32(const crc32_shift_pack_t *sp, mck_join32_t a, mck_join32_t b, uint32_t init)
+{
+    mck_join32_t e;
+    e.r = mck_seed32(sp, b.r, a.r, init, b.n);
+    e.n = a.n + b.n;
+    return e;
+}
+
+MCK_HD mck_join64_t
+mck_join64(const crc64_shift_pack_t *sp, mck_join64_t a, mck_join64_t b, uint64_t init)
+{
+    mck_join64_t e;
+    e.r = mck_seed64(sp, b.r, a.r, init, b.n);
+    e.n = a.n + b.n;
+    return e;
+}
+
+MCK_HD uint32_t
+mck_join_out32(mck_join32_t e, uint32_t xorout, int msb)
+{
+    return mck_reg_to_crc32(e.r, xorout, msb);
+}
+
+MCK_HD uint64_t
+mck_join_out64(mck_join64_t e, uint64_t xorout, int msb)
+{
+    return mck_reg_to_crc64(e.r, xorout, msb);
 }
 
 /* Host only: a catalogue model in the kernels' form.  A reflected model as

@@ -571,6 +571,181 @@ __global__ __launch_bounds__(256) void combine_kernel(const T *a, const T *b, co
     }
 }
 
+// ---- combine_runs: the CRCs of a run's chunks joined in order ----
+// The join is crc_gpu_seed.h's monoid over (r, n); what is decided here is the
+// bracketing.  W lanes share one run of K chunks: lane l folds the l-th of W
+// contiguous slices of ceil(K / W) chunks left to right -- every lane a chain
+// of its own, so the 64 chains of a wave advance together --, then the lanes'
+// elements meet in an ordered tree, log2(W) joins deep: a shuffle down by 1,
+// 2, 4, ..., the lower lane the left operand.  A run of K chunks has K / W +
+// log2(W) joins on its critical path, and a run of up to W chunks the tree
+// alone.
+// A workgroup is four waves and takes four consecutive runs, a wave each
+// (W = 64).  A run of more than kJoinBlockRun chunks is taken by the whole
+// workgroup instead (W = 256: the four wave results meet in LDS).  Which runs
+// are long is read once per workgroup, into LDS, so every wave takes the same
+// branches around the barriers whatever happens to the table meanwhile.
+constexpr uint32_t kJoinWaves = 4;           // waves, and runs, per workgroup
+constexpr uint64_t kJoinBlockRun = 4096;     // longer runs: the workgroup, not one wave
+constexpr uint32_t kJoinMaxGrid = 65536;     // workgroups stride past this many
+
+template <typename T>
+struct JoinOps;
+template <>
+struct JoinOps<uint32_t> {
+    using E = mck_join32_t;
+    using SP = crc32_shift_pack_t;
+    static __device__ __forceinline__ E in(uint32_t v, uint64_t n, uint32_t init, uint32_t xorout, int msb) {
+        return mck_join_in32(v, n, init, xorout, msb);
+    }
+    static __device__ __forceinline__ E join(const SP *sp, E a, E b, uint32_t init) { return mck_join32(sp, a, b, init); }
+    static __device__ __forceinline__ uint32_t out(E e, uint32_t xorout, int msb) { return mck_join_out32(e, xorout, msb); }
+    // lane l reads lane (l + d) % 64's word: one ds_bpermute_b32, what __shfl lowers to.  (The builtin, not
+    // __shfl_down: a second user with a run-time distance made hipcc invert a compare and its select in the
+    // CRC-64 batch kernels' lane combine -- equivalent code, but not the shipped instruction stream.)
+    static __device__ __forceinline__ uint32_t shfl_down(uint32_t r, int d) {
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x + d) & 63u) << 2), (int)r);
+    }
+};
+template <>
+struct JoinOps<uint64_t> {
+    using E = mck_join64_t;
+    using SP = crc64_shift_pack_t;
+    static __device__ __forceinline__ E in(uint64_t v, uint64_t n, uint64_t init, uint64_t xorout, int msb) {
+        return mck_join_in64(v, n, init, xorout, msb);
+    }
+    static __device__ __forceinline__ E join(const SP *sp, E a, E b, uint64_t init) { return mck_join64(sp, a, b, init); }
+    static __device__ __forceinline__ uint64_t out(E e, uint64_t xorout, int msb) { return mck_join_out64(e, xorout, msb); }
+    static __device__ __forceinline__ uint64_t shfl_down(uint64_t r, int d) {  // the 32-bit halves
+        const uint32_t lo = JoinOps<uint32_t>::shfl_down((uint32_t)r, d),
+                       hi = JoinOps<uint32_t>::shfl_down((uint32_t)(r >> 32), d);
+        return (uint64_t)hi << 32 | lo;
+    }
+};
+
+template <typename T>
+struct JoinArgs {
+    const T *crc;           // chunk k's finalized CRC
+    const uint64_t *len;    // and byte count
+    const void *shift;      // the model's Z^n pack
+    T init, xorout;
+    int msb;
+};
+
+// Lane `lane` of `width` folds its slice of chunks [lo, hi), left to right.
+// The next chunk's words are loaded before the join that waits for this one's tables.
+template <typename T>
+__device__ __forceinline__ typename JoinOps<T>::E join_slice(const JoinArgs<T> &a, uint64_t lo, uint64_t hi, uint32_t lane,
+                                                             uint32_t width) {
+    using J = JoinOps<T>;
+    const typename J::SP *sp = reinterpret_cast<const typename J::SP *>(a.shift);
+    const uint64_t k = hi - lo, m = (k + width - 1) / width;
+    const uint64_t s0 = (uint64_t)lane * m, s1 = s0 + m;  // (k <= 2^31, lane < 256)
+    const uint64_t b = lo + (s0 < k ? s0 : k), e = lo + (s1 < k ? s1 : k);
+    if (b >= e) return J::in(0, 0, a.init, a.xorout, a.msb);  // the identity
+    typename J::E acc = J::in(a.crc[b], a.len[b], a.init, a.xorout, a.msb);
+    if (b + 1 >= e) return acc;
+    T v = a.crc[b + 1];
+    uint64_t n = a.len[b + 1];
+    for (uint64_t i = b + 1; i < e; i++) {
+        const typename J::E x = J::in(v, n, a.init, a.xorout, a.msb);
+        if (i + 1 < e) {
+            v = a.crc[i + 1];
+            n = a.len[i + 1];
+        }
+        acc = J::join(sp, acc, x, a.init);
+    }
+    return acc;
+}
+
+// The wave's 64 elements joined in lane order; the result is lane 0's.  Step
+// d joins lane l (a multiple of 2d, holding lanes [l, l + d)) with lane l + d
+// (holding [l + d, l + 2d)); the other lanes' elements are no longer needed.
+template <typename T>
+__device__ __forceinline__ typename JoinOps<T>::E join_wave(const JoinArgs<T> &a, typename JoinOps<T>::E e, uint32_t lane) {
+    using J = JoinOps<T>;
+    const typename J::SP *sp = reinterpret_cast<const typename J::SP *>(a.shift);
+#pragma unroll 1
+    for (int d = 1; d < 64; d <<= 1) {
+        typename J::E o;
+        o.r = J::shfl_down(e.r, d);
+        o.n = JoinOps<uint64_t>::shfl_down(e.n, d);
+        if ((lane & (2 * d - 1)) == 0) e = J::join(sp, e, o, a.init);
+    }
+    return e;
+}
+
+// out and out_len must not overlap the tables: runs are joined in parallel
+template <typename T>
+__global__ __launch_bounds__(256) void combine_runs_kernel(JoinArgs<T> a, uint64_t nchunks, const uint64_t *first,
+                                                           uint64_t nruns, T *out, uint64_t *out_len) {
+    using J = JoinOps<T>;
+    __shared__ uint64_t s_first[kJoinWaves + 1];
+    __shared__ T s_r[kJoinWaves];
+    __shared__ uint64_t s_n[kJoinWaves];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t ngroups = (nruns + kJoinWaves - 1) / kJoinWaves;
+    for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const uint64_t j0 = g * kJoinWaves;
+        const uint32_t nr = nruns - j0 < kJoinWaves ? (uint32_t)(nruns - j0) : kJoinWaves;
+        // the group's run bounds, clamped to the chunk tables: no read past them
+        if (threadIdx.x <= nr) {
+            const uint64_t f = first[j0 + threadIdx.x];
+            s_first[threadIdx.x] = f < nchunks ? f : nchunks;
+        }
+        __syncthreads();
+        uint64_t my_lo = 0, my_hi = 0;
+        bool mine = false;
+        for (uint32_t w = 0; w < nr; w++) {  // (block-uniform: nr and s_first)
+            const uint64_t lo = s_first[w], hi = s_first[w + 1] > lo ? s_first[w + 1] : lo;
+            if (hi - lo <= kJoinBlockRun) {
+                if (w == wave) {
+                    my_lo = lo;
+                    my_hi = hi;
+                    mine = true;
+                }
+                continue;
+            }
+            typename J::E e = join_wave<T>(a, join_slice<T>(a, lo, hi, threadIdx.x, 256), lane);
+            if (lane == 0) {
+                s_r[wave] = e.r;
+                s_n[wave] = e.n;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (uint32_t v = 1; v < kJoinWaves; v++) {
+                    typename J::E o;
+                    o.r = s_r[v];
+                    o.n = s_n[v];
+                    e = J::join(reinterpret_cast<const typename J::SP *>(a.shift), e, o, a.init);
+                }
+                out[j0 + w] = J::out(e, a.xorout, a.msb);
+                if (out_len) out_len[j0 + w] = e.n;
+            }
+            __syncthreads();  // s_r, s_n are free again
+        }
+        if (mine) {
+            const typename J::E e = join_wave<T>(a, join_slice<T>(a, my_lo, my_hi, lane, 64), lane);
+            if (lane == 0) {
+                out[j0 + wave] = J::out(e, a.xorout, a.msb);
+                if (out_len) out_len[j0 + wave] = e.n;
+            }
+        }
+        __syncthreads();  // s_first is free again
+    }
+}
+
+template <typename T>
+hipError_t launch_combine_runs(const crc_rmodel_t &rm, const void *shift, const void *dev_crc, const uint64_t *dev_len,
+                               size_t nchunks, const uint64_t *dev_run_first, size_t nruns, void *dev_out,
+                               uint64_t *dev_out_len, void *stream) {
+    const JoinArgs<T> a{(const T *)dev_crc, dev_len, shift, (T)rm.rinit, (T)rm.xorout, rm.msb};
+    const uint64_t groups = ((uint64_t)nruns + kJoinWaves - 1) / kJoinWaves;
+    return launch_kernel(combine_runs_kernel<T>, dim3(groups > kJoinMaxGrid ? kJoinMaxGrid : (unsigned)groups), dim3(256),
+                         (hipStream_t)stream, nullptr, a, (uint64_t)nchunks, dev_run_first, (uint64_t)nruns, (T *)dev_out,
+                         dev_out_len);
+}
+
 // Common front of the element calls: the count cap, the device, the model
 // (its kernels' form in *rm) and the device context.
 int state_call(const char *method, size_t count, Model *m, crc_rmodel_t *rm, DevCtx **c) {
@@ -847,6 +1022,27 @@ int mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a, const 
                                       (uint32_t *)dev_out, (uint64_t)count, shift, (uint32_t)rm.rinit,
                                       (uint32_t)rm.xorout, rm.msb);
     return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "combine");
+}
+
+int mchecksum_gpu_combine_runs(const char *hash_method, const void *dev_crc, const uint64_t *dev_len, size_t nchunks,
+                               const uint64_t *dev_run_first, size_t nruns, void *dev_out, uint64_t *dev_out_len,
+                               void *stream) {
+    if ((nruns && (!dev_run_first || !dev_out)) || (nchunks && (!dev_crc || !dev_len)))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if ((uint64_t)nchunks > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 chunks in one call");
+    Model m;
+    crc_rmodel_t rm;
+    DevCtx *c = nullptr;
+    if (int rc = state_call(hash_method, nruns, &m, &rm, &c)) return rc;  // (nruns <= 2^31, the device, the method)
+    const void *shift = nullptr;
+    if (int rc = get_ext(c, m.idx, &shift)) return rc;
+    if (nruns == 0) return MCHECKSUM_GPU_OK;
+    // no work-queue slot, no workspace, no device-side wait: nothing to fail closed on
+    const hipError_t e = m.width == 64 ? launch_combine_runs<uint64_t>(rm, shift, dev_crc, dev_len, nchunks, dev_run_first,
+                                                                       nruns, dev_out, dev_out_len, stream)
+                                       : launch_combine_runs<uint32_t>(rm, shift, dev_crc, dev_len, nchunks, dev_run_first,
+                                                                       nruns, dev_out, dev_out_len, stream);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "combine_runs");
 }
 
 const char *mchecksum_gpu_last_error(void) { return t_err; }

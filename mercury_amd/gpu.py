@@ -342,6 +342,64 @@ def combine(method: str, crc_a: torch.Tensor, crc_b: torch.Tensor, len_b: torch.
     return out
 
 
+def _check_i64_table(t, name: str, count: int | None = None):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous()
+            or (count is not None and t.numel() < count)):
+        raise GpuChecksumError(f"{name} must be a contiguous device int64 tensor"
+                               + (f" of at least {count} elements" if count is not None else ""))
+
+
+def combine_runs(method: str, crc: torch.Tensor, lens: torch.Tensor, run_first: torch.Tensor,
+                 out: torch.Tensor | None = None, out_len=None, stream=None, run_first_host=None):
+    """The CRC of every run of chunks, in one launch (mchecksum_gpu_combine_runs):
+    chunk k has the finalized CRC crc[k] and lens[k] bytes (device int64); run
+    j is chunks run_first[j] : run_first[j+1] (nruns + 1 non-decreasing device
+    int64 indices <= the number of chunks), and out[j] the CRC of those chunks'
+    bytes concatenated in order.  A zero-length chunk counts for nothing,
+    whatever its CRC word; an empty run gets the CRC of the empty message.
+
+    Returns out -- or (out, out_len) when out_len is given: True for a new
+    tensor, or a device int64 tensor of nruns elements, which receives every
+    run's byte total.  (out, out_len) are valid (crc, lens) of a further call.
+    out and out_len must not overlap crc, lens or run_first.  Pass
+    run_first_host (a host copy) to have the table validated before launch;
+    otherwise it is trusted, as in the C ABI."""
+    nchunks = crc.numel() if isinstance(crc, torch.Tensor) else 0
+    _check_state(crc, method, nchunks, "crc")
+    _check_i64_table(lens, "lens", nchunks)
+    _check_i64_table(run_first, "run_first")
+    nruns = run_first.numel() - 1
+    if nruns < 0:
+        raise GpuChecksumError("run_first needs at least one entry")
+    if run_first_host is not None:
+        import numpy as np
+        fh = np.asarray(run_first_host, dtype=np.uint64)
+        if fh.ndim != 1 or len(fh) != run_first.numel():
+            raise GpuChecksumError("run_first_host does not match run_first")
+        if np.any(fh[1:] < fh[:-1]):
+            raise GpuChecksumError("run_first must be non-decreasing")
+        if int(fh[-1]) > nchunks:
+            raise GpuChecksumError("run_first extends past the last chunk")
+    if out is None:
+        out = torch.empty(nruns, dtype=out_dtype(method), device=crc.device)
+    _check_state(out, method, nruns, "out")
+    if out_len is True:
+        out_len = torch.empty(nruns, dtype=torch.int64, device=crc.device)
+    elif out_len is False:
+        out_len = None
+    if out_len is not None:
+        _check_i64_table(out_len, "out_len", nruns)
+    _same_device(crc, lens=lens, run_first=run_first, out=out, out_len=out_len)
+    with _on(crc):
+        rc = _lib().mchecksum_gpu_combine_runs(method.encode(), crc.data_ptr(), lens.data_ptr(), nchunks,
+                                               run_first.data_ptr(), nruns, out.data_ptr(),
+                                               out_len.data_ptr() if out_len is not None else None,
+                                               _stream_handle(stream, crc.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_combine_runs")
+    return out if out_len is None else (out, out_len)
+
+
 def verify_offsets(method: str, data: torch.Tensor, offsets: torch.Tensor, expected: torch.Tensor,
                    stream=None, offsets_host=None):
     """Returns (status uint8 per payload: 1 = mismatch, mismatch count tensor)."""
