@@ -168,12 +168,7 @@ __device__ __forceinline__ uint64_t combine64_lane0(const uint8_t *lds, const cr
     return x;
 }
 
-// USER: no effect on the code -- a kernel family added to a file names its own
-// instantiation, so that a family already there keeps the only call of its own
-// (seg_copy_kernel beside seg_kernel<64>: with a second caller of one
-// instantiation the compiler orders seg_kernel<64>'s fill differently, and
-// tools/batch_kernel_pairs.py could no longer show it unchanged).
-template <int BLOCK, int OM, int USER = 0>
+template <int BLOCK, int OM>
 __device__ void fill_lds64(uint8_t *lds, const crc64_gpu_pack_t *pk) {
     uint64_t *l = reinterpret_cast<uint64_t *>(lds);
     uint4 *l4 = reinterpret_cast<uint4 *>(lds);

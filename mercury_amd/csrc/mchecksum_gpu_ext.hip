@@ -32,7 +32,7 @@
 #include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
-#include "seg_copy_plan.h"
+#include "seg_plan.h"
 
 namespace {
 
@@ -41,7 +41,7 @@ namespace {
 // Object j = the concatenation of segments [first[j], first[j+1]).  By
 // linearity (register form, crc_gpu_layout.h):
 //   CRC(object) = Z^N(init) ^ XOR_c Z^(after_c)(L(chunk_c)) ^ xorout
-// where chunks of at most kChunk bytes tile every segment, L is the CRC with
+// where chunks of at most kSegChunk bytes (seg_plan.h) tile every segment, L is the CRC with
 // zero init and no finalisation, N is the object's byte count and after_c the
 // number of object bytes that follow chunk c.  Short scan launches write the
 // segment lengths' byte and chunk prefix sums (caller's workspace) and preset
@@ -60,33 +60,40 @@ namespace {
 // 256 KiB chunks: enough of them to fill the chip from a single GiB-sized
 // segment, while the shift (a few us of dependent scalar loads) stays a few
 // percent of a chunk's scan time.  A chunk that ends its object needs no shift.
-constexpr uint64_t kChunk = 256u << 10;
-static_assert(kChunk == mck::kSegChunk, "seg_copy_plan.h cuts segments as the chunk passes do");
+//
+// seg_plan.h is the one home of the passes' arithmetic: the chunk size, the
+// workspace's layout (seg_work_layout; the host fills SegWork from it, and
+// both kernels' arguments carry that one struct), and the chunk record
+// (SegChunk) with every rule and guard that fills it.  This file keeps the
+// loads, the payload loops and the launches.
+using mck::kDescWords;
+using mck::kNoObj;
+using mck::kScanBlk;
+using mck::kScanPer;
+using mck::kScanThreads;
+using mck::kSegChunk;
+using mck::seg_chunk_count;
+using mck::SegChunk;
+using mck::SegWork;
 
 struct SegArgs {
     const uint64_t *addr, *len;
     uint64_t nseg;
     const uint64_t *first;
     uint64_t nobj;
-    const uint64_t *P, *C;  // workspace: byte / chunk exclusive prefix sums, nseg + 1 each
-    const unsigned long long *ragged;  // workspace: non-zero if any chunk needs the ragged loop
-    // workspace: per segment s, {its object j (kNoObj outside [first[0],
-    // first[nobj])), first[j], first[j + 1], the object's head segment (its
-    // first non-empty one; kNoObj when the scan block could not tell)} (4
-    // words: one scalar load in the queue pass), and the segment of each chunk
-    // while the chunks fit map_cap
-    const uint64_t *obj;
-    const uint32_t *map;
-    uint64_t map_cap;
+    // the workspace (seg_plan.h).  Per segment s its object record is {its
+    // object j (kNoObj outside [first[0], first[nobj])), first[j], first[j +
+    // 1], the object's head segment (its first non-empty one; kNoObj when the
+    // scan block could not tell)}: 4 words, one scalar load in the queue pass.
+    // map_cap: the part of the map this call uses (0: the pass searches C).
+    SegWork w;
     void *out;
     const void *pack, *shift;
     // work-queue slot of the chunk passes (crc_gpu_queue.h, WgQueue; nullptr:
     // static split) and the caller's fail-closed word
     unsigned long long *queue;
     uint32_t *err_word;
-    // the scan's fault report of this call (ScanArgs): claim == scan_key(epoch,
-    // *gen - 1) means the scan gave up, so the chunk pass hashes nothing
-    const uint64_t *fault_claim, *gen;
+    // the call's look-back epoch (scan_key; scan_gave_up)
     uint64_t epoch;
 };
 
@@ -123,10 +130,7 @@ struct SegArgs {
 // kernel boundary), round 2 as three.  (1 or 2 segments per scan thread --
 // 4x / 2x the scan blocks -- measured +-0.1% on the bench's 32768-segment
 // lists, profiles/r05/scan_per/.)
-constexpr uint32_t kScanThreads = 256, kScanPer = 4, kScanBlk = kScanThreads * kScanPer;
-constexpr uint32_t kDescWords = 8;  // per scan block: flag, aggregate (p, c, r), inclusive (p, c, r), pad
-
-__device__ __forceinline__ uint64_t seg_chunks(uint64_t l) { return (l + kChunk - 1) / kChunk; }
+// (kScanThreads, kScanPer, kScanBlk and the descriptors' kDescWords: seg_plan.h)
 
 // Block-wide inclusive scan of (p, c) over the first 256 threads (a wider
 // block's other threads only take part in the barrier); returns the block
@@ -165,8 +169,6 @@ __device__ __forceinline__ void block_scan2(uint64_t &p, uint64_t &c, uint64_t *
     *tp = sp;
     *tc = sc;
 }
-
-constexpr uint64_t kNoObj = ~0ull;
 
 // One wave: the largest index j < n with a[j] <= key (a sorted ascending,
 // a[0] <= key), by 64-ary narrowing: each round probes 64 evenly spaced
@@ -299,23 +301,20 @@ __device__ __forceinline__ bool seg_lookback(uint64_t *desc, uint64_t b, uint64_
 struct ScanArgs {
     const uint64_t *len, *addr;
     uint64_t nseg;
-    uint64_t *desc;
     uint64_t epoch;
-    uint64_t *P, *C;
-    unsigned long long *ragged;
     const uint64_t *first;
     uint64_t nobj;
-    uint64_t *obj;
-    uint32_t *map;
-    uint64_t map_cap;
+    SegWork w;  // the workspace, as the chunk pass gets it; obj nullptr: no object records (CRC-32C)
     void *out;
     uint32_t width;
     uint64_t preset;
     uint32_t *err_word;
-    uint64_t *fault_claim;  // workspace word: the call's key once a fault was reported
-    uint64_t *gen;          // workspace word: calls scanned in this workspace (the key's second half)
     uint64_t fault_block;
 };
+// The scan is the workspace's one writer: its view of the same regions, and
+// the one place where they become writable.
+using ScanWork = mck::SegWorkT<uint64_t, uint32_t>;
+__device__ __forceinline__ ScanWork scan_work(const SegWork &w) { return __builtin_bit_cast(ScanWork, w); }
 // A call's key: its epoch and the workspace's call count.  A graph replays
 // its captured epoch, so the epoch alone cannot tell two replays apart
 // (ADVICE r5); the count moves on every scan, captured or not.
@@ -327,9 +326,9 @@ __device__ __forceinline__ uint64_t scan_key(uint64_t epoch, uint64_t gen) {
 // swap the call's key into the claim word reports, the rest see it already
 // there -- and the chunk pass, seeing it, hashes nothing (fail closed, and
 // no second deadline in the same call).
-__device__ __forceinline__ void report_scan_fault(const ScanArgs &sa, uint64_t gen) {
+__device__ __forceinline__ void report_scan_fault(const ScanArgs &sa, const ScanWork &ws, uint64_t gen) {
     const uint64_t key = scan_key(sa.epoch, gen);
-    const uint64_t was = __hip_atomic_exchange(sa.fault_claim, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t was = __hip_atomic_exchange(ws.fault_claim, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (was != key && sa.err_word) atomicAdd(sa.err_word, 1u);
 }
 // LDS scratch of one scan block: the object rows of its segments (4 x u64 +
@@ -341,6 +340,7 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const bool act = tid < kScanThreads;
     const uint64_t nseg = sa.nseg, nobj = sa.nobj;
+    const ScanWork ws = scan_work(sa.w);
     const uint64_t s0 = b * kScanBlk, s1 = s0 + kScanBlk < nseg ? s0 + kScanBlk : nseg;
     uint64_t *row = reinterpret_cast<uint64_t *>(scratch);
     uint64_t *row_f0 = row + kScanBlk, *row_f1 = row_f0 + kScanBlk;  // the object's first[j], first[j + 1]
@@ -360,13 +360,13 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
         const uint64_t i = s0 + tid * kScanPer + e;
         l[e] = act && i < nseg ? sa.len[i] : 0;
         p += l[e];
-        c += seg_chunks(l[e]);
+        c += seg_chunk_count(l[e]);
         r |= act && i < nseg && l[e] && (l[e] % 1024 != 0 || sa.addr[i] % 16 != 0);
     }
     // the objects touching this block (queue pass only)
     const uint64_t f0 = sa.first[0], f1 = sa.first[nobj];
     const uint64_t lo_s = s0 > f0 ? s0 : f0, hi_s = s1 < f1 ? s1 : f1;
-    if (sa.obj && lo_s < hi_s) {
+    if (ws.obj && lo_s < hi_s) {
         if (w == 1) {
             const uint64_t jb = wave_last_le(sa.first, nobj + 1, lo_s, lane);
             if (lane == 0) bc[0] = jb;
@@ -388,26 +388,26 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
         // last block bumps it only after its look-back saw every block's
         // descriptor, so all blocks of the call read the same count -- and
         // tag their descriptors with it: the key's low 62 bits above the state
-        const uint64_t gen = uniform(ld_relaxed(sa.gen));
+        const uint64_t gen = uniform(ld_relaxed(ws.gen));
         uint64_t ep, ec, er;
-        const bool ok = seg_lookback(sa.desc, b, scan_key(sa.epoch, gen) << 2, tp, tc, *rag, lane, &ep, &ec, &er,
+        const bool ok = seg_lookback(ws.desc, b, scan_key(sa.epoch, gen) << 2, tp, tc, *rag, lane, &ep, &ec, &er,
                                      sa.fault_block);
         if (lane == 0) {
             ex[0] = ep;
             ex[1] = ec;
             ex[2] = er;
-            if (!ok) report_scan_fault(sa, gen);  // fail closed: the scan is not trustworthy
-            if (b + 1 == nb) st_relaxed(sa.gen, gen + 1);
+            if (!ok) report_scan_fault(sa, ws, gen);  // fail closed: the scan is not trustworthy
+            if (b + 1 == nb) st_relaxed(ws.gen, gen + 1);
         }
     }
     __syncthreads();
     if (b + 1 == nb && tid == 0) {
-        sa.P[nseg] = ex[0] + tp;
-        sa.C[nseg] = ex[1] + tc;
-        *sa.ragged = ex[2] | *rag;
+        ws.P[nseg] = ex[0] + tp;
+        ws.C[nseg] = ex[1] + tc;
+        *ws.ragged = ex[2] | *rag;
     }
     uint64_t ep = ex[0] + p - p0, ec = ex[1] + c - c0;
-    if (sa.obj) {
+    if (ws.obj) {
         if (act) {
             for (uint32_t t = tid; t < kScanBlk; t += kScanThreads) row[t] = kNoObj;
 #pragma unroll
@@ -444,25 +444,25 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
     for (uint32_t e = 0; e < kScanPer; e++) {
         const uint64_t i = s0 + tid * kScanPer + e;
         if (i < nseg) {
-            sa.P[i] = ep;
-            sa.C[i] = ec;
-            if (sa.obj) {
+            ws.P[i] = ep;
+            ws.C[i] = ec;
+            if (ws.obj) {
                 const uint64_t t = i - s0;
-                sa.obj[4 * i] = row[t];
+                ws.obj[4 * i] = row[t];
                 if (row[t] != kNoObj) {
-                    sa.obj[4 * i + 1] = row_f0[t];
-                    sa.obj[4 * i + 2] = row_f1[t];
-                    sa.obj[4 * i + 3] = row_hs[t];
+                    ws.obj[4 * i + 1] = row_f0[t];
+                    ws.obj[4 * i + 2] = row_f1[t];
+                    ws.obj[4 * i + 3] = row_hs[t];
                 }
             }
             // chunk -> segment map, while it fits (the chunk passes check the
             // total against map_cap and search C otherwise)
-            const uint64_t ce = ec + seg_chunks(l[e]);
-            if (ce <= sa.map_cap)
-                for (uint64_t k = ec; k < ce; k++) sa.map[k] = (uint32_t)i;
+            const uint64_t ce = ec + seg_chunk_count(l[e]);
+            if (ce <= ws.map_cap)
+                for (uint64_t k = ec; k < ce; k++) ws.map[k] = (uint32_t)i;
         }
         ep += l[e];
-        ec += seg_chunks(l[e]);
+        ec += seg_chunk_count(l[e]);
     }
 }
 
@@ -471,6 +471,19 @@ __global__ __launch_bounds__(kScanThreads) void seg_scan(ScanArgs sa) {
     scan_block(sa, blockIdx.x, gridDim.x, scratch);
 }
 
+
+// Chunk c of segment s, as a pass found s: the chunk's bytes (k->addr, k->n)
+// and its offset in the segment, or false.  (A scan whose look-back gave up --
+// reported on the error word -- leaves tables that may not fit the list: such
+// a chunk is skipped, never read out of bounds.  The rules: seg_plan.h.)
+__device__ __forceinline__ bool seg_chunk_of(const SegArgs &a, uint64_t s, uint64_t c, uint64_t *off, SegChunk *k) {
+    const bool ok = mck::seg_segment_ok(s, a.nseg);
+    const uint64_t cs = ok ? a.w.C[s] : ~0ull, L = ok ? a.len[s] : 0;
+    k->in = false;
+    if (!mck::seg_chunk_bytes(c, cs, L, off, &k->n)) return false;
+    k->addr = a.addr[s] + *off;
+    return true;
+}
 
 // A wave's contiguous range of chunks [c, c1), walked in order.  The segment
 // and object indices only advance, so a chunk costs a few cached scalar loads
@@ -483,37 +496,23 @@ struct ChunkWalk {
     __device__ __forceinline__ ChunkWalk(const SegArgs &args, uint32_t wave, uint32_t nw, uint64_t nchunks) : a(&args) {
         c = nchunks * wave / nw;
         c1 = nchunks * (wave + 1) / nw;
-        s = c < c1 ? lower_bound_u64(a->C, a->nseg + 1, c + 1) - 1 : 0;
+        s = c < c1 ? lower_bound_u64(a->w.C, a->nseg + 1, c + 1) - 1 : 0;
         j = c < c1 && s >= a->first[0] ? lower_bound_u64(a->first, a->nobj + 1, s + 1) - 1 : 0;
     }
 
-    // Next chunk: its bytes [addr, addr + n) and, when its segment belongs to
-    // an object (*in), the object, the object bytes that follow it (*end -
-    // *stop, as seg_locate) and whether it starts the object (*head).
-    __device__ __forceinline__ bool next(uint64_t *addr, uint64_t *n, bool *in, uint64_t *obj, uint64_t *end, uint64_t *stop,
-                         bool *head) {
+    // Next chunk, placed in its object (k->in: hash it).
+    __device__ __forceinline__ bool next(SegChunk *k) {
         if (c >= c1) return false;
-        while (s < a->nseg && a->C[s + 1] <= c) s++;  // skips empty segments
-        const uint64_t cs = s < a->nseg ? a->C[s] : ~0ull, L = s < a->nseg ? a->len[s] : 0;
-        const uint64_t off = (c - cs) * kChunk;
-        if (cs > c || off >= L) {  // maps of a failed scan (reported): skip, never read out of bounds
-            *in = false;
-            c++;
-            return true;
-        }
-        *addr = a->addr[s] + off;
-        *n = L - off < kChunk ? L - off : kChunk;
-        *in = s >= a->first[0] && s < a->first[a->nobj];
-        if (*in) {
+        while (s < a->nseg && a->w.C[s + 1] <= c) s++;  // skips empty segments
+        uint64_t off;
+        if (seg_chunk_of(*a, s, c, &off, k) && s >= a->first[0] && s < a->first[a->nobj]) {
             while (j + 1 < a->nobj && a->first[j + 1] <= s) j++;
-            *obj = j;
-            *end = a->P[a->first[j + 1]];
-            *stop = a->P[s] + off + *n;
-            *head = a->P[s] + off == a->P[a->first[j]];
-            // an untrusted scan again: prefixes that put the chunk past its
-            // object's end would shift by a wrapped count (shift32 indexes
-            // its operators by that count's hex digits, 12 of them held)
-            if (*stop > *end) *in = false;
+            k->obj = j;
+            k->at = a->w.P[s] + off;
+            k->obj_at = a->w.P[a->first[j]];
+            k->end = a->w.P[a->first[j + 1]];
+            k->head = mck::seg_chunk_head(kNoObj, s, off, k->at, k->obj_at);
+            k->in = mck::seg_chunk_place(k);
         }
         c++;
         return true;
@@ -530,54 +529,63 @@ struct ChunkWalk {
 // VGPR spills and it measured 5% slower than the static ranges
 // (profiles/r02/ab_seg_queue.log).
 //
-// Chunk c (< nchunks): its bytes [addr, addr + n) and, when its segment
-// belongs to an object (*in), the object, the object bytes after it (*end -
-// *stop) and whether it starts the object (*head).  c is wave-uniform, so
-// every load is scalar: the map, then the segment's words and its 4-word
-// object record.  The object's end offset (*end) is a third dependent load,
-// but the payload loop does not wait for it -- the caller subtracts only
-// after the loop (round 4: the head test from the record's head segment
-// instead of the object's start offset, a second third-round load).  Only a
-// chunk whose object's head the scan block could not place compares byte
-// offsets.  Locate latency is not what limits the pass: two rounds instead
+// Chunk c (< nchunks): its bytes and, when its segment belongs to an object
+// (k->in), the object, its byte offsets and whether it starts the object.  c
+// is wave-uniform, so every load is scalar: the map, then the segment's words
+// and its 4-word object record.  The object's end offset (k->end) is a third
+// dependent load, but the payload loop does not wait for it: without PLACE
+// the caller applies seg_chunk_after only after the loop (round 4: the head
+// test from the record's head segment instead of the object's start offset, a
+// second third-round load).  Only a chunk whose object's head the scan block
+// could not place compares byte offsets -- or, PLACE, a copying pass, which
+// needs the object's start offset for the chunk's place anyway and has the
+// chunk placed here.  Locate latency is not what limits the pass: two rounds instead
 // of three measured within noise, and so did a one-round locate of bench.py's
 // seg layout from the chunk index alone; the same layout with a constant
 // chunk length measured +1.6-2.5% -- the compile-time trip count gave the
 // payload loop whole-ring code (payload64_even, crc_gpu_crc64.h), now taken
 // for every chunk of whole rings (profiles/r04/ab_seg_locate_bound.log,
 // ab_seg_cheats.log, ab_seg_full.log, ab_seg_head.log, ab_seg_even.log).
-__device__ __forceinline__ void seg_locate(const SegArgs &a, uint64_t c, uint64_t nchunks, uint64_t *addr,
-                                           uint64_t *n, bool *in, uint64_t *obj, uint64_t *end, uint64_t *stop,
-                                           bool *head) {
-    const uint64_t s = nchunks <= a.map_cap ? (uint64_t)a.map[c] : lower_bound_u64(a.C, a.nseg + 1, c + 1) - 1;
-    // (a scan whose look-back gave up -- reported on the error word -- leaves
-    // maps that may not fit: such a chunk is skipped, never read out of bounds)
-    const uint64_t cs = s < a.nseg ? a.C[s] : ~0ull, L = s < a.nseg ? a.len[s] : 0;
-    const uint64_t off = (c - cs) * kChunk;
-    if (cs > c || off >= L) {
-        *in = false;
-        return;
-    }
-    *addr = a.addr[s] + off;
-    *n = L - off < kChunk ? L - off : kChunk;
-    const uint64_t *o4 = a.obj + 4 * s;  // {j, first[j], first[j + 1], head segment}
-    const uint64_t j = o4[0];
-    *in = j != kNoObj;
-    if (*in) {
-        *obj = j;
-        const uint64_t at = a.P[s] + off;
-        *end = a.P[o4[2]];
-        *stop = at + *n;
-        const uint64_t hs = o4[3];
-        *head = hs != kNoObj ? hs == s && off == 0 : at == a.P[o4[1]];
-    }
+template <bool PLACE>
+__device__ __forceinline__ void seg_locate(const SegArgs &a, uint64_t c, uint64_t nchunks, SegChunk *k) {
+    const uint64_t s = nchunks <= a.w.map_cap ? (uint64_t)a.w.map[c] : lower_bound_u64(a.w.C, a.nseg + 1, c + 1) - 1;
+    uint64_t off;
+    if (!seg_chunk_of(a, s, c, &off, k)) return;
+    const uint64_t *o4 = a.w.obj + 4 * s;  // {j, first[j], first[j + 1], head segment}
+    const uint64_t j = o4[0], fs = o4[1], ls = o4[2], hs = o4[3];
+    if (!mck::seg_record_ok(j, a.nobj, fs, ls, a.nseg)) return;
+    k->obj = j;
+    k->at = a.w.P[s] + off;
+    k->end = a.w.P[ls];
+    k->obj_at = PLACE || !mck::seg_head_known(hs) ? a.w.P[fs] : 0;
+    k->head = mck::seg_chunk_head(hs, s, off, k->at, k->obj_at);
+    k->in = PLACE ? mck::seg_chunk_place(k) : true;
 }
-// The first segment of the object of chunk c, which seg_locate placed in an
-// object (the copying pass: the chunk's place in its object counts from
-// there): seg_locate's segment again, then the second word of its record.
-__device__ __forceinline__ uint64_t seg_locate_first(const SegArgs &a, uint64_t c, uint64_t nchunks) {
-    const uint64_t s = nchunks <= a.map_cap ? (uint64_t)a.map[c] : lower_bound_u64(a.C, a.nseg + 1, c + 1) - 1;
-    return a.obj[4 * s + 1];
+
+// The scan of this call gave up (reported on the error word, report_scan_fault):
+// the chunk pass hashes nothing and writes nothing.
+__device__ __forceinline__ bool scan_gave_up(const SegArgs &a) {
+    return uniform(ld_relaxed(a.w.fault_claim)) == scan_key(a.epoch, uniform(ld_relaxed(a.w.gen)) - 1);
+}
+
+// A hashed chunk's epilogue: x, the chunk's register on the wave's lanes, is
+// made uniform, completed for a head chunk shorter than the register (the
+// init it could not carry in its first W/8 bytes comes in as Z^n(init)),
+// shifted over the object bytes after the chunk and XORed into the object's
+// output -- with init once more for a head chunk, cancelling the preset's.
+template <int W, class Pack, class Shift, class Reg>
+__device__ __forceinline__ void seg_emit(const Pack *pk, const Shift *sp, void *out, Reg init, Reg x, const SegChunk &k,
+                                         uint32_t lane) {
+    x = uniform(x);
+    if (k.head && k.n < W / 8) x ^= pk->zinit[k.n];
+    if constexpr (W == 32) {
+        x = shift32(sp, x, k.after);
+        if (lane == 0) atomicXor(reinterpret_cast<uint32_t *>(out) + k.obj, k.head ? x ^ init : x);
+    } else {
+        x = shift64(sp, x, k.after);
+        if (lane == 0)
+            atomicXor(reinterpret_cast<unsigned long long *>(out) + k.obj, (unsigned long long)(k.head ? x ^ init : x));
+    }
 }
 
 // The chunk passes, one launch after the scan: one 1024-thread workgroup per
@@ -599,25 +607,14 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWPB + (threadIdx.x >> 6));
     const uint32_t nw = gridDim.x * kWPB;
-    const uint64_t nchunks = uniform(a.C[a.nseg]);
+    const uint64_t nchunks = uniform(a.w.C[a.nseg]);
     // the CRC-64 pass takes chunks from the work queue (the host passes a
     // slot; without one, for_each_unit strides statically)
     constexpr bool kQueue = W == 64;
     __shared__ WgQueue wgq;
     if (kQueue && threadIdx.x == 0) wg_queue_init(&wgq, a.queue, nchunks);
-    // the scan of this call gave up (reported on the error word): hash nothing
-    // -- after the queue's init, which readies the slot's other bank
-    if (uniform(ld_relaxed(a.fault_claim)) == scan_key(a.epoch, uniform(ld_relaxed(a.gen)) - 1)) return;
-    // CRC-32C: calls body(addr, n, j, end, stop, head) for every chunk of
-    // this wave's static range that belongs to an object.
-    auto chunks = [&](auto &&body) -> bool {
-        ChunkWalk walk(a, wave, nw, nchunks);
-        uint64_t p, n, j = 0, end = 0, stop = 0;
-        bool in, head = false;
-        while (walk.next(&p, &n, &in, &j, &end, &stop, &head))
-            if (in) body(p, n, j, end, stop, head);
-        return false;
-    };
+    // hash nothing -- after the queue's init, which readies the slot's other bank
+    if (scan_gave_up(a)) return;
     if constexpr (W == 32) {
         uint8_t *lds_raw = lds_tab;
         const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -626,26 +623,26 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         __syncthreads();
         const Tab32<false> lds{lds_raw};
         const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
-        uint32_t *out = reinterpret_cast<uint32_t *>(a.out);
-        const bool nt = uniform(a.P[a.nseg]) >= kSegNtBytes;  // as for CRC-64 below
+        const bool nt = uniform(a.w.P[a.nseg]) >= kSegNtBytes;  // as for CRC-64 below
         const uint32_t init = pk->init;
-        const bool faulted = chunks([&](uint64_t p, uint64_t n, uint64_t j, uint64_t end, uint64_t stop, bool head) {
-            const uint8_t *q = reinterpret_cast<const uint8_t *>(p);
+        // every chunk of this wave's static range that belongs to an object
+        ChunkWalk walk(a, wave, nw, nchunks);
+        SegChunk k;
+        while (walk.next(&k)) {
+            if (!k.in) continue;
+            const uint8_t *q = reinterpret_cast<const uint8_t *>(k.addr);
+            const uint64_t n = k.n;
             // whole rings of 1 KiB steps from a 16-B aligned start (the usual
             // bulk segment) take the aligned loop: no edge masks, no pad operator
-            const bool aligned = p % 16 == 0 && n % (1024u * kRing) == 0 && n != 0;
+            const bool aligned = k.addr % 16 == 0 && n % (1024u * kRing) == 0 && n != 0;
             // the object's first chunk starts from the register init (in its
-            // first 4 bytes; Z^n(init) for a shorter chunk)
-            const uint32_t reg = head && n >= 4 ? init : 0u;
-            uint32_t x = aligned && nt    ? payload32_aligned<6, true>(lds, q, n >> 10, lane, lc0, lc1, reg)
-                         : aligned        ? payload32_aligned<6, false>(lds, q, n >> 10, lane, lc0, lc1, reg)
-                                          : payload32_g64<false, Tab32<false>, true>(lds, pk, q, n, lane, lc0, lc1, reg);
-            x = uniform(x);
-            if (head && n < 4) x ^= pk->zinit[n];
-            x = shift32(sp, x, end - stop);  // (the object bytes after the chunk)
-            if (lane == 0) atomicXor(out + j, head ? x ^ init : x);  // ^ init: cancels the preset's
-        });
-        if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
+            // first 4 bytes; Z^n(init) for a shorter chunk: seg_emit)
+            const uint32_t reg = k.head && n >= 4 ? init : 0u;
+            const uint32_t x = aligned && nt ? payload32_aligned<6, true>(lds, q, n >> 10, lane, lc0, lc1, reg)
+                               : aligned     ? payload32_aligned<6, false>(lds, q, n >> 10, lane, lc0, lc1, reg)
+                                             : payload32_g64<false, Tab32<false>, true>(lds, pk, q, n, lane, lc0, lc1, reg);
+            seg_emit<32>(pk, sp, a.out, init, x, k, lane);
+        }
     } else {
         uint8_t *lds = lds_tab;
         const crc64_gpu_pack_t *pk = reinterpret_cast<const crc64_gpu_pack_t *>(a.pack);
@@ -653,13 +650,12 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         fill_lds64<1024, kOpsLds>(lds, pk);
         __syncthreads();
         const uint32_t lc = (lane & 31u) << 3;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(a.out);
         // Non-temporal payload loads once the batch is far larger than the
         // Infinity Cache, as for fixed batches.  Here the size is only known on
         // the device (the segment scan's total), so the choice is a uniform
         // branch per chunk: +3% on `seg` (duplicating the whole walk under one
         // branch measured the same and spills more).
-        const bool nt = uniform(a.P[a.nseg]) >= kSegNtBytes;
+        const bool nt = uniform(a.w.P[a.nseg]) >= kSegNtBytes;
         const uint64_t init = pk->init;
         // Pipelined (round 6, as the split CRC-64 pieces): a chunk of whole
         // rings from an aligned start (every chunk of a list of 16-B aligned
@@ -667,17 +663,16 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         // the wave takes the next chunk and issues its first loads as soon as
         // the current step loop ends, before the current chunk's lane combine,
         // Z^n shift and output XOR.  Other chunks run on their own.
-        struct Chunk {
-            uint64_t p = 0, n = 0, j = 0, end = 0, stop = 0;
-            bool in = false, head = false, even = false;
+        struct Chunk : SegChunk {
+            bool even = false;
         };
         auto locate = [&](uint64_t c, Chunk *k) {
-            seg_locate(a, c, nchunks, &k->p, &k->n, &k->in, &k->j, &k->end, &k->stop, &k->head);
-            k->even = k->in && k->p % 16 == 0 && k->n % (1024u * kRing64) == 0 && k->n >= 2048u * kRing64;
+            seg_locate<false>(a, c, nchunks, k);
+            k->even = k->in && k->addr % 16 == 0 && k->n % (1024u * kRing64) == 0 && k->n >= 2048u * kRing64;
         };
         auto issue = [&](uint4 (&ring)[kRing64], const Chunk &k) {
-            if (nt) ring64_load<true>(ring, reinterpret_cast<const uint8_t *>(k.p), lane);
-            else ring64_load<false>(ring, reinterpret_cast<const uint8_t *>(k.p), lane);
+            if (nt) ring64_load<true>(ring, reinterpret_cast<const uint8_t *>(k.addr), lane);
+            else ring64_load<false>(ring, reinterpret_cast<const uint8_t *>(k.addr), lane);
         };
         UnitTaker<ChunkPlan> tk(&wgq, a.queue, nchunks, wave, nw, false, ChunkPlan(nchunks, gridDim.x));
         Lane64 ln = lane64(lc);
@@ -688,18 +683,18 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         if (have) locate(c, &cur);
         if (have && cur.even) issue(ring, cur);
         while (have) {
-            // an untrusted scan (seg_locate): prefixes that put the chunk past
+            // an untrusted scan (seg_plan.h): prefixes that put the chunk past
             // its object's end would shift by a wrapped count (shift64 indexes
             // its operators by that count's hex digits, 12 of them held) --
             // skipped as the others.  Tested here, not in locate(): the next
             // chunk's first loads do not wait for its object's end offset.
-            if (cur.in && cur.stop > cur.end) cur.in = cur.even = false;
-            const uint8_t *q = reinterpret_cast<const uint8_t *>(cur.p);
+            if (cur.in && !mck::seg_chunk_after(&cur)) cur.in = cur.even = false;
+            const uint8_t *q = reinterpret_cast<const uint8_t *>(cur.addr);
             // the object's first chunk starts from the register init (in its
-            // first 8 bytes; Z^n(init) for a shorter, ragged chunk)
+            // first 8 bytes; Z^n(init) for a shorter, ragged chunk: seg_emit)
             const uint64_t reg = cur.head && cur.n >= 8 ? init : 0ull;
             uint64_t x = 0, x0 = 0, x1 = 0;
-            const bool aligned = cur.p % 16 == 0 && cur.n % 1024 == 0;
+            const bool aligned = cur.addr % 16 == 0 && cur.n % 1024 == 0;
             if (cur.even) {
                 if (nt) fold64_ring<true>(lds, ring, q, (uint32_t)(cur.n >> 10), lane, ln, reg, &x0, &x1);
                 else fold64_ring<false>(lds, ring, q, (uint32_t)(cur.n >> 10), lane, ln, reg, &x0, &x1);
@@ -715,10 +710,7 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
             if (next && nxt.even) issue(ring, nxt);  // in flight during the combine below
             if (cur.in) {
                 if (cur.even) x = combine64<6, kOpsLds>(lds, pk, x0, x1, lane);
-                x = uniform(x);
-                if (!aligned && cur.head && cur.n < 8) x ^= pk->zinit[cur.n];
-                x = shift64(sp, x, cur.end - cur.stop);  // (the object bytes after the chunk)
-                if (lane == 0) atomicXor(out + cur.j, (unsigned long long)(cur.head ? x ^ init : x));  // ^ init: cancels the preset's
+                seg_emit<64>(pk, sp, a.out, init, x, cur, lane);
             }
             cur = nxt;
             have = next;
@@ -731,7 +723,7 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
 // The copying chunk passes (mchecksum_gpu_gather_segments, _scatter_segments):
 // seg_kernel's walk, head-chunk rule, shift and output XOR, with every chunk
 // also stored on the other side by the payload loop that hashes it, so each
-// byte is read once.  DIR (seg_copy_plan.h): gather loads the chunk from its
+// byte is read once.  DIR (seg_plan.h): gather loads the chunk from its
 // segment and stores it at its place in the object's contiguous range,
 // scatter the reverse; the hashed bytes are the loaded ones either way.  The
 // chunk's place in its object is P[s] + off - P[first[j]]: one more scalar
@@ -759,14 +751,19 @@ __global__ __launch_bounds__(1024, 1) void seg_copy_kernel(SegCopyArgs ca) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWPB + (threadIdx.x >> 6));
     const uint32_t nw = gridDim.x * kWPB;
-    const uint64_t nchunks = uniform(a.C[a.nseg]);
+    const uint64_t nchunks = uniform(a.w.C[a.nseg]);
     __shared__ WgQueue wgq;
     if (W == 64 && threadIdx.x == 0) wg_queue_init(&wgq, a.queue, nchunks);
-    // the scan of this call gave up (reported on the error word): hash nothing
-    // and, ahead of the first store below, write nothing
-    if (uniform(ld_relaxed(a.fault_claim)) == scan_key(a.epoch, uniform(ld_relaxed(a.gen)) - 1)) return;
-    const bool nt = uniform(a.P[a.nseg]) >= kSegNtBytes;  // as seg_kernel
+    // hash nothing and, ahead of the first store below, write nothing
+    if (scan_gave_up(a)) return;
+    const bool nt = uniform(a.w.P[a.nseg]) >= kSegNtBytes;  // as seg_kernel
     const uint64_t flat = reinterpret_cast<uint64_t>(ca.flat);
+    // a placed chunk's addresses: where the payload loop loads and stores it
+    auto sides = [&](const SegChunk &k, const uint8_t **q, uint8_t **d) {
+        const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, k.addr, flat, ca.starts[k.obj], k.obj_off);
+        *q = reinterpret_cast<const uint8_t *>(ad.load);
+        *d = reinterpret_cast<uint8_t *>(ad.store);
+    };
     if constexpr (W == 32) {
         uint8_t *lds_raw = lds_tab;
         const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
@@ -775,54 +772,40 @@ __global__ __launch_bounds__(1024, 1) void seg_copy_kernel(SegCopyArgs ca) {
         __syncthreads();
         const Tab32<false> lds{lds_raw};
         const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
-        uint32_t *out = reinterpret_cast<uint32_t *>(a.out);
         const uint32_t init = pk->init;
         ChunkWalk walk(a, wave, nw, nchunks);
-        uint64_t p, n, j = 0, end = 0, stop = 0;
-        bool in, head = false;
-        while (walk.next(&p, &n, &in, &j, &end, &stop, &head)) {
-            if (!in) continue;
-            const uint64_t at = stop - n, obj_at = a.P[a.first[j]];
-            if (at < obj_at) continue;  // an untrusted scan, as stop > end in the walk: no store anywhere
-            const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, p, flat, ca.starts[j], at, obj_at);
-            const uint8_t *q = reinterpret_cast<const uint8_t *>(ad.load);
-            uint8_t *d = reinterpret_cast<uint8_t *>(ad.store);
-            const uint32_t reg = head && n >= 4 ? init : 0u;
-            uint32_t x = nt ? payload32_g64<true, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d)
-                            : payload32_g64<false, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d);
-            x = uniform(x);
-            if (head && n < 4) x ^= pk->zinit[n];
-            x = shift32(sp, x, end - stop);
-            if (lane == 0) atomicXor(out + j, head ? x ^ init : x);
+        SegChunk k;
+        while (walk.next(&k)) {
+            if (!k.in) continue;  // (a chunk the walk could not place is stored nowhere)
+            const uint8_t *q;
+            uint8_t *d;
+            sides(k, &q, &d);
+            const uint64_t n = k.n;
+            const uint32_t reg = k.head && n >= 4 ? init : 0u;
+            const uint32_t x = nt ? payload32_g64<true, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d)
+                                  : payload32_g64<false, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d);
+            seg_emit<32>(pk, sp, a.out, init, x, k, lane);
         }
     } else {
         uint8_t *lds = lds_tab;
         const crc64_gpu_pack_t *pk = reinterpret_cast<const crc64_gpu_pack_t *>(a.pack);
         const crc64_shift_pack_t *sp = reinterpret_cast<const crc64_shift_pack_t *>(a.shift);
-        fill_lds64<1024, kOpsLds, /*USER*/ 1>(lds, pk);  // (an instantiation of its own: crc_gpu_crc64.h)
+        fill_lds64<1024, kOpsLds>(lds, pk);
         __syncthreads();
         const uint32_t lc = (lane & 31u) << 3;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(a.out);
         const uint64_t init = pk->init;
         auto one = [&](uint64_t c) {
-            uint64_t p = 0, n = 0, j = 0, end = 0, stop = 0;
-            bool in = false, head = false;
-            seg_locate(a, c, nchunks, &p, &n, &in, &j, &end, &stop, &head);
-            if (!in || stop > end) return;  // (an untrusted scan, as seg_kernel)
-            const uint64_t fs = seg_locate_first(a, c, nchunks);
-            if (fs > a.nseg) return;
-            const uint64_t at = stop - n, obj_at = a.P[fs];
-            if (at < obj_at) return;
-            const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, p, flat, ca.starts[j], at, obj_at);
-            const uint8_t *q = reinterpret_cast<const uint8_t *>(ad.load);
-            uint8_t *d = reinterpret_cast<uint8_t *>(ad.store);
-            const uint64_t reg = head && n >= 8 ? init : 0ull;
-            uint64_t x = nt ? payload64_g64<true, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d)
-                            : payload64_g64<false, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d);
-            x = uniform(x);
-            if (head && n < 8) x ^= pk->zinit[n];
-            x = shift64(sp, x, end - stop);
-            if (lane == 0) atomicXor(out + j, (unsigned long long)(head ? x ^ init : x));
+            SegChunk k;
+            seg_locate<true>(a, c, nchunks, &k);
+            if (!k.in) return;
+            const uint8_t *q;
+            uint8_t *d;
+            sides(k, &q, &d);
+            const uint64_t n = k.n;
+            const uint64_t reg = k.head && n >= 8 ? init : 0ull;
+            const uint64_t x = nt ? payload64_g64<true, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d)
+                                  : payload64_g64<false, true, kOpsLds, true>(lds, pk, q, n, lane, lc, reg, d);
+            seg_emit<64>(pk, sp, a.out, init, x, k, lane);
         };
         const bool faulted = for_each_unit<true>(&wgq, a.queue, nchunks, wave, nw, one);
         if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
@@ -1175,25 +1158,12 @@ using namespace mck;
 
 extern "C" {
 
-// P, C (nseg + 1 each), the ragged flag, the scan's fault claim, the workspace's
-// call count, a spare word, the look-back descriptor of
-// each scan block (kDescWords), each segment's object and its bounds in
-// first[] and its head segment (4 nseg), then the chunk -> segment map (u32 entries:
-// 4 per segment + 64 Ki, i.e. lists averaging up to ~1 MiB per segment, or
-// one huge segment up to 16 GiB; none past 2^32 segments).  More than 2^40
-// segments (far beyond device memory) is rejected, so the size cannot wrap:
-// SIZE_MAX then makes any allocation of it fail.
-constexpr uint64_t kMaxSegs = 1ull << 40;
-uint64_t seg_map_cap(uint64_t nseg) { return nseg < (1ull << 32) ? 4 * nseg + 65536 : 0; }
 // Test builds (MCK_QFAULT_TEST): MCHECKSUM_GPU_QFAULT_SCAN=b makes scan block
 // b give up its look-back -- or, with MCHECKSUM_GPU_QFAULT_MODE=scanstall,
 // never publish its descriptor (tests/test_gpu_fail_closed.py); ~0 = none.
 uint64_t scan_fault_block() {
     return MCK_QFAULT_TEST ? mck_settings()->qfault_scan : ~0ull;
 }
-// scan blocks of a list (one at least: the scan launch writes the totals)
-uint64_t seg_blocks(uint64_t nseg) { return nseg ? (nseg + kScanBlk - 1) / kScanBlk : 1; }
-uint64_t seg_words(uint64_t nseg) { return 2 * (nseg + 1) + 4 + kDescWords * seg_blocks(nseg) + 4 * nseg; }
 // The scan's look-back epochs: a process-wide counter from a random seed, so a
 // workspace's descriptors from any earlier call (this process or, through
 // reused memory, another) never match the current call's.
@@ -1209,132 +1179,132 @@ uint64_t scan_epoch() {
     }()};
     return ctr.fetch_add(1, std::memory_order_relaxed) & ((1ull << 61) - 1);
 }
-size_t mchecksum_gpu_segments_work_size(size_t nseg) {
-    if ((uint64_t)nseg > kMaxSegs) return SIZE_MAX;
-    return sizeof(uint64_t) * seg_words(nseg) + sizeof(uint32_t) * seg_map_cap(nseg);
-}
+// (the workspace's layout: seg_work_layout, seg_plan.h)
+size_t mchecksum_gpu_segments_work_size(size_t nseg) { return seg_work_bytes(nseg); }
 
-// checksum_segments, gather_segments and scatter_segments: the argument
-// checks, the scan launch and the chunk pass -- seg_kernel, or for a copying
-// call (dir = mck::kSegGather / kSegScatter, with the contiguous side dev_flat
-// and its dev_starts table) seg_copy_kernel under the same launch policy.
+// One segment call: checksum_segments, or with a direction (mck::kSegGather /
+// kSegScatter), the contiguous side and its starts table, a copying call.
 constexpr int kSegHashOnly = -1;
-static int seg_copy_call(const char *hash_method, int dir, void *dev_flat, const uint64_t *dev_starts,
-                         const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
-                         const uint64_t *dev_obj_first, size_t nobj, void *dev_work, size_t work_size, void *dev_out,
-                         void *stream) {
-    const bool copy = dir != kSegHashOnly;
-    if (!dev_obj_first || (nobj && !dev_out) || (nseg && (!dev_seg_addr || !dev_seg_len)) || !dev_work ||
-        (copy && nobj && (!dev_flat || !dev_starts)))
+struct SegCall {
+    const char *method;
+    const uint64_t *seg_addr, *seg_len;
+    size_t nseg;
+    const uint64_t *obj_first;
+    size_t nobj;
+    void *work;
+    size_t work_size;
+    void *out;
+    void *stream;
+    int dir = kSegHashOnly;
+    void *flat = nullptr;              // gather: the destination; scatter: the source
+    const uint64_t *starts = nullptr;  // nobj byte offsets into it
+};
+
+// The front of the three segment entry points: the argument checks, the scan
+// launch and the chunk pass -- seg_kernel, or for a copying call
+// seg_copy_kernel under the same launch policy.
+static int seg_call(const SegCall &sc) {
+    const bool copy = sc.dir != kSegHashOnly;
+    const size_t nseg = sc.nseg, nobj = sc.nobj;
+    if (!sc.obj_first || (nobj && !sc.out) || (nseg && (!sc.seg_addr || !sc.seg_len)) || !sc.work ||
+        (copy && nobj && (!sc.flat || !sc.starts)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if ((uint64_t)nseg > kMaxSegs) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^40 segments in one call");
-    if (work_size < mchecksum_gpu_segments_work_size(nseg) || (uintptr_t)dev_work % 8)
+    if (sc.work_size < mchecksum_gpu_segments_work_size(nseg) || (uintptr_t)sc.work % 8)
         return set_err(MCHECKSUM_GPU_EINVAL, "workspace smaller than mchecksum_gpu_segments_work_size() or unaligned");
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
     Model m;
     DevCtx *c = nullptr;
     const void *pack = nullptr, *shift = nullptr;
-    int rc = resolve_model(hash_method, &m);
+    int rc = resolve_model(sc.method, &m);
     if (!rc) rc = device_ctx(&c);
     if (!rc) rc = get_pack(c, m.idx, CRC_GPU_MAX_LOG2G, &pack);
     if (!rc) rc = get_ext(c, m.idx, &shift);
     if (rc) return rc;
     const int width = m.width;
     if (nobj == 0) return MCHECKSUM_GPU_OK;
-    hipStream_t s = (hipStream_t)stream;
     SegArgs a{};
-    a.addr = dev_seg_addr;
-    a.len = dev_seg_len;
+    a.addr = sc.seg_addr;
+    a.len = sc.seg_len;
     a.nseg = nseg;
-    a.first = dev_obj_first;
+    a.first = sc.obj_first;
     a.nobj = nobj;
-    a.P = (const uint64_t *)dev_work;
-    a.C = (const uint64_t *)dev_work + (nseg + 1);
-    a.ragged = (const unsigned long long *)dev_work + 2 * (nseg + 1);
-    const uint64_t nb = seg_blocks(nseg);
-    uint64_t *desc = (uint64_t *)dev_work + 2 * (nseg + 1) + 4;
-    a.obj = desc + kDescWords * nb;
-    a.map = reinterpret_cast<const uint32_t *>((const uint64_t *)dev_work + seg_words(nseg));
+    a.w = seg_work(sc.work, nseg);
     // only the CRC-64 queue pass reads the map; MCHECKSUM_GPU_SEG_MAP_CAP caps
     // the part of it used (tests: 0 forces the search over C)
-    a.map_cap = width == 64 ? seg_map_cap(nseg) : 0;
-    {
-        const uint64_t v = mck_settings()->gpu_seg_map_cap;
-        a.map_cap = v < a.map_cap ? v : a.map_cap;
-    }
-    a.out = dev_out;
+    const uint64_t cap = width == 64 ? a.w.map_cap : 0, v = mck_settings()->gpu_seg_map_cap;
+    a.w.map_cap = v < cap ? v : cap;
+    a.out = sc.out;
     a.pack = pack;
     a.shift = shift;
     a.err_word = error_word();
-    a.fault_claim = (const uint64_t *)dev_work + 2 * (nseg + 1) + 1;
-    a.gen = (const uint64_t *)dev_work + 2 * (nseg + 1) + 2;
+    a.epoch = scan_epoch();
     // every object starts as the CRC of the empty message, init ^ xorout in
     // the kernels' register form (MSB-first models: byte-reversed, swapped
     // back with the outputs below)
     const crc_rmodel_t rm = gpu_rmodel(m.idx);
-    const uint64_t preset = rm.rinit ^ rm.xorout;
     ScanArgs sa{};
-    sa.len = dev_seg_len;
-    sa.addr = dev_seg_addr;
+    sa.len = sc.seg_len;
+    sa.addr = sc.seg_addr;
     sa.nseg = nseg;
-    sa.desc = desc;
-    sa.epoch = a.epoch = scan_epoch();
-    sa.P = (uint64_t *)a.P;
-    sa.C = (uint64_t *)a.C;
-    sa.ragged = (unsigned long long *)a.ragged;
-    sa.first = dev_obj_first;
+    sa.epoch = a.epoch;
+    sa.first = sc.obj_first;
     sa.nobj = nobj;
-    sa.obj = width == 64 ? (uint64_t *)a.obj : nullptr;
-    sa.map = (uint32_t *)a.map;
-    sa.map_cap = a.map_cap;
-    sa.out = dev_out;
+    sa.w = a.w;
+    if (width != 64) sa.w.obj = nullptr;  // only the queue pass reads the object records
+    sa.out = sc.out;
     sa.width = (uint32_t)width;
-    sa.preset = preset;
+    sa.preset = rm.rinit ^ rm.xorout;
     sa.err_word = a.err_word;
-    sa.fault_claim = (uint64_t *)a.fault_claim;
-    sa.gen = (uint64_t *)a.gen;
     sa.fault_block = scan_fault_block();
-    hipError_t e = launch_kernel(seg_scan, dim3((unsigned)nb), dim3(kScanThreads), s, nullptr, sa);
+    hipError_t e = launch_kernel(seg_scan, dim3((unsigned)seg_scan_blocks(nseg)), dim3(kScanThreads),
+                                 (hipStream_t)sc.stream, nullptr, sa);
     if (e != hipSuccess) return hip_err(e, "segment scan launch");
     SlotRef sr;  // only the CRC-64 pass takes chunks from a work queue
-    if (width == 64) sr = queue_slot(c, stream);
+    if (width == 64) sr = queue_slot(c, sc.stream);
     a.queue = sr.q;
     if (!copy) {
-        rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, stream, a,
+        rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, sc.stream, a,
                          "segment kernel launch");
     } else {
-        const SegCopyArgs ca{a, (uint8_t *)dev_flat, dev_starts};
-        const bool gather = dir == mck::kSegGather;
+        const SegCopyArgs ca{a, (uint8_t *)sc.flat, sc.starts};
+        const bool gather = sc.dir == mck::kSegGather;
         auto k = width == 32 ? (gather ? seg_copy_kernel<32, mck::kSegGather> : seg_copy_kernel<32, mck::kSegScatter>)
                              : (gather ? seg_copy_kernel<64, mck::kSegGather> : seg_copy_kernel<64, mck::kSegScatter>);
-        rc = launch_slot(c, sr, k, (unsigned)c->cus, 1024, stream, ca, "segment copy kernel launch");
+        rc = launch_slot(c, sr, k, (unsigned)c->cus, 1024, sc.stream, ca, "segment copy kernel launch");
     }
     // MSB-first model: the kernels' values are the CRCs byte-swapped (crc_gpu_layout.h)
-    if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(dev_out, nobj, width, stream);
+    if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(sc.out, nobj, width, sc.stream);
     return rc;
 }
 
 int mchecksum_gpu_checksum_segments(const char *hash_method, const uint64_t *dev_seg_addr,
                                     const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
                                     size_t nobj, void *dev_work, size_t work_size, void *dev_out, void *stream) {
-    return seg_copy_call(hash_method, kSegHashOnly, nullptr, nullptr, dev_seg_addr, dev_seg_len, nseg, dev_obj_first,
-                         nobj, dev_work, work_size, dev_out, stream);
+    return seg_call({hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_out,
+                     stream});
 }
 
 int mchecksum_gpu_gather_segments(const char *hash_method, const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len,
                                   size_t nseg, const uint64_t *dev_obj_first, size_t nobj, void *dev_dst,
                                   const uint64_t *dev_dst_starts, void *dev_work, size_t work_size, void *dev_out,
                                   void *stream) {
-    return seg_copy_call(hash_method, mck::kSegGather, dev_dst, dev_dst_starts, dev_seg_addr, dev_seg_len, nseg,
-                         dev_obj_first, nobj, dev_work, work_size, dev_out, stream);
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_out, stream};
+    sc.dir = mck::kSegGather;
+    sc.flat = dev_dst;
+    sc.starts = dev_dst_starts;
+    return seg_call(sc);
 }
 
 int mchecksum_gpu_scatter_segments(const char *hash_method, const void *dev_src, const uint64_t *dev_src_starts,
                                    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
                                    const uint64_t *dev_obj_first, size_t nobj, void *dev_work, size_t work_size,
                                    void *dev_out, void *stream) {
-    return seg_copy_call(hash_method, mck::kSegScatter, const_cast<void *>(dev_src), dev_src_starts, dev_seg_addr,
-                         dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_out, stream);
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_out, stream};
+    sc.dir = mck::kSegScatter;
+    sc.flat = const_cast<void *>(dev_src);
+    sc.starts = dev_src_starts;
+    return seg_call(sc);
 }
 
 // verify_core_headers and seal_core_headers: the argument checks, the 16-bit

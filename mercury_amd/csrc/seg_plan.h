@@ -1,0 +1,197 @@
+// seg_plan.h -- the arithmetic of the segment passes (checksum_segments,
+// gather_segments, scatter_segments; mchecksum_gpu_ext.hip): how a segment is
+// cut into chunks, where each region of the caller's workspace lies, which
+// bytes a chunk covers and where it sits in its object -- with every guard
+// that keeps a chunk pass inside the caller's memory when the scan's tables
+// cannot be trusted -- and a chunk's two addresses in a copying call.  Pure
+// arithmetic, like launch_plan.h and copy_plan.h: the kernels include it, and
+// the host compiler walks it on the CPU (tests/native/seg_plan.cpp) together
+// with the store rule (crc_gpu_pack_store.h).  Plain C++ compiles it.
+//
+// Object j = segments [first[j], first[j + 1]) in order; P and C are the
+// exclusive prefix sums of the segment lengths and chunk counts (the scan's).
+// A chunk is bytes [off, off + n) of segment s, off a multiple of the chunk
+// size.  It starts at
+//   segment side:    addr[s] + off
+//   contiguous side: base + starts[j] + (P[s] + off - P[first[j]])
+// and the direction says which of the two is loaded and which is stored.
+//
+// The functions below take values the kernels have already loaded; when and
+// where each word is loaded stays the kernels' business (seg_locate).  A scan
+// whose look-back gave up leaves the workspace as some earlier call wrote it:
+// tables that are valid for ANOTHER list.  A chunk pass that runs on them must
+// read and write only inside the caller's segments, so every word taken from
+// the workspace is checked here before it becomes an index, a length or a
+// shift count, and a chunk that fails a check is skipped.  A trusted scan
+// never trips one.
+#ifndef MCK_SEG_PLAN_H
+#define MCK_SEG_PLAN_H
+
+#include <cstddef>
+#include <cstdint>
+
+#include "crc_gpu_shape.h"
+
+namespace mck {
+
+// gather: segments -> contiguous; scatter: contiguous -> segments
+enum SegCopyDir : int { kSegGather, kSegScatter };
+
+// The segment passes' chunk size.  CH is a parameter so that a test can make
+// chunk edges dense.
+constexpr uint64_t kSegChunk = 256u << 10;
+
+template <uint64_t CH = kSegChunk>
+MCK_HOST_DEVICE_INLINE uint64_t seg_chunk_count(uint64_t len) {
+    return (len + CH - 1) / CH;
+}
+// bytes of the chunk at offset off (< len) of a segment of len bytes
+template <uint64_t CH = kSegChunk>
+MCK_HOST_DEVICE_INLINE uint64_t seg_chunk_len(uint64_t len, uint64_t off) {
+    return len - off < CH ? len - off : CH;
+}
+
+// The scan launch: kScanThreads threads take kScanPer segments each, and every
+// scan block keeps kDescWords look-back words in the workspace: flag,
+// aggregate (p, c, r), inclusive (p, c, r), pad.
+constexpr uint32_t kScanThreads = 256, kScanPer = 4, kScanBlk = kScanThreads * kScanPer;
+constexpr uint32_t kDescWords = 8;
+// scan blocks of a list (one at least: the scan launch writes the totals)
+MCK_HOST_DEVICE_INLINE uint64_t seg_scan_blocks(uint64_t nseg) { return nseg ? (nseg + kScanBlk - 1) / kScanBlk : 1; }
+
+// More segments than this (far beyond device memory) are rejected, so the
+// workspace size cannot wrap.
+constexpr uint64_t kMaxSegs = 1ull << 40;
+
+// The caller's workspace, as 8-byte word offsets of its regions in order: P
+// and C (nseg + 1 words each), the ragged flag, the scan's fault claim, the
+// workspace's count of scans (gen), a spare word, the look-back descriptors
+// (kDescWords per scan block), each segment's object record {object, first[j],
+// first[j + 1], head segment} (4 nseg), then the chunk -> segment map: map_cap
+// u32 entries, 4 per segment + 64 Ki, i.e. lists averaging up to ~1 MiB per
+// segment, or one huge segment up to 16 GiB; none from 2^32 segments on (an
+// entry could not hold the index).  fault_claim and gen live across calls:
+// where they sit is part of what one call leaves to the next.
+struct SegWorkLayout {
+    uint64_t P, C, ragged, fault_claim, gen, spare, desc, obj, map;
+    uint64_t map_cap;
+    uint64_t bytes;
+};
+MCK_HOST_DEVICE_INLINE SegWorkLayout seg_work_layout(uint64_t nseg) {
+    SegWorkLayout w{};
+    w.P = 0;
+    w.C = w.P + (nseg + 1);
+    w.ragged = w.C + (nseg + 1);
+    w.fault_claim = w.ragged + 1;
+    w.gen = w.fault_claim + 1;
+    w.spare = w.gen + 1;
+    w.desc = w.spare + 1;
+    w.obj = w.desc + kDescWords * seg_scan_blocks(nseg);
+    w.map = w.obj + 4 * nseg;
+    w.map_cap = nseg < (1ull << 32) ? 4 * nseg + 65536 : 0;
+    w.bytes = 8 * w.map + 4 * w.map_cap;
+    return w;
+}
+// what mchecksum_gpu_segments_work_size returns: SIZE_MAX makes any
+// allocation of it fail
+MCK_HOST_DEVICE_INLINE size_t seg_work_bytes(uint64_t nseg) {
+    return nseg > kMaxSegs ? SIZE_MAX : (size_t)seg_work_layout(nseg).bytes;
+}
+
+// The workspace's regions as pointers, shared by the scan (which writes them
+// through its own writable view) and the chunk passes (which only read).
+template <class U64, class U32>
+struct SegWorkT {
+    U64 *P, *C;        // byte / chunk exclusive prefix sums, nseg + 1 each
+    U64 *ragged;       // non-zero if any chunk needs the ragged loop
+    U64 *fault_claim;  // the key of the call whose scan reported a fault
+    U64 *gen;          // scans run in this workspace (the key's second half)
+    U64 *desc;         // look-back descriptors
+    U64 *obj;          // object records, 4 words per segment
+    U32 *map;          // the segment of each chunk, while the chunks fit map_cap
+    uint64_t map_cap;
+};
+using SegWork = SegWorkT<const uint64_t, const uint32_t>;
+inline SegWork seg_work(const void *base, uint64_t nseg) {
+    const SegWorkLayout l = seg_work_layout(nseg);
+    const uint64_t *w = static_cast<const uint64_t *>(base);
+    return SegWork{w + l.P,   w + l.C,   w + l.ragged, w + l.fault_claim,
+                   w + l.gen, w + l.desc, w + l.obj,    reinterpret_cast<const uint32_t *>(w + l.map), l.map_cap};
+}
+
+// A segment outside every object, and an object whose head segment the scan
+// block could not place (object records, words 0 and 3).
+constexpr uint64_t kNoObj = ~0ull;
+
+// A chunk as the chunk passes hold it: what the pass loaded (at, obj_at, end:
+// byte offsets in the list's order, from P) and what the rules below make of it.
+struct SegChunk {
+    uint64_t addr = 0, n = 0;  // its bytes [addr, addr + n) on the segment side
+    uint64_t obj = 0;          // its object
+    uint64_t at = 0;           // its first byte: P[s] + off
+    uint64_t obj_at = 0;       // its object's first byte, P[first[obj]] (where the pass loads it)
+    uint64_t end = 0;          // its object's end, P[first[obj + 1]]
+    uint64_t after = 0;        // object bytes that follow it: its Z^n shift count (seg_chunk_after)
+    uint64_t obj_off = 0;      // its offset in the object (seg_chunk_place)
+    bool in = false;           // belongs to an object and passed every check so far: hash it
+    bool head = false;         // starts its object
+};
+
+// The segment index a pass found for a chunk, and the words of that segment's
+// object record: each may index the tables only inside them (P and C have
+// nseg + 1 entries, out and starts nobj).
+MCK_HOST_DEVICE_INLINE bool seg_segment_ok(uint64_t s, uint64_t nseg) { return s < nseg; }
+MCK_HOST_DEVICE_INLINE bool seg_record_ok(uint64_t obj, uint64_t nobj, uint64_t fs, uint64_t ls, uint64_t nseg) {
+    return obj < nobj && fs <= nseg && ls <= nseg;  // (kNoObj is no object)
+}
+
+// Bytes of chunk c inside its segment: cs = C[s], len = len[s].  false: the
+// chunk is not one of that segment's -- skip it.  (A difference that wraps in
+// the product still passes only with off < len: the bytes are the segment's.)
+template <uint64_t CH = kSegChunk>
+MCK_HOST_DEVICE_INLINE bool seg_chunk_bytes(uint64_t c, uint64_t cs, uint64_t len, uint64_t *off, uint64_t *n) {
+    *off = (c - cs) * CH;
+    if (cs > c || *off >= len) return false;
+    *n = seg_chunk_len<CH>(len, *off);
+    return true;
+}
+
+// The shift packs hold the operators of 12 base-16 digits (CRC_SHIFT_DIGITS):
+// a count from 2^48 on would index past them.
+constexpr uint64_t kSegShiftEnd = 1ull << 48;
+
+// The chunk's place in its object: the object bytes that follow it ...
+MCK_HOST_DEVICE_INLINE bool seg_chunk_after(SegChunk *k) {
+    k->after = k->end - k->at - k->n;
+    return k->at <= k->end && k->n <= k->end - k->at && k->after < kSegShiftEnd;
+}
+// ... and its offset in the object (k->obj_at loaded too).  false from either:
+// prefixes that put the chunk outside its object -- skip it.
+MCK_HOST_DEVICE_INLINE bool seg_chunk_place(SegChunk *k) {
+    k->obj_off = k->at - k->obj_at;
+    return seg_chunk_after(k) && k->at >= k->obj_at;
+}
+
+// Whether a chunk starts its object: it is the first chunk of the object's
+// head segment hs (its first non-empty one), or, where the scan block could
+// not tell (kNoObj), it lies at the object's first byte.
+MCK_HOST_DEVICE_INLINE bool seg_head_known(uint64_t hs) { return hs != kNoObj; }
+MCK_HOST_DEVICE_INLINE bool seg_chunk_head(uint64_t hs, uint64_t s, uint64_t off, uint64_t at, uint64_t obj_at) {
+    return seg_head_known(hs) ? hs == s && off == 0 : at == obj_at;
+}
+
+struct SegCopyAddr {
+    uint64_t load, store;
+};
+
+// seg_at = addr[s] + off; obj_off: the chunk's offset in its object
+// (seg_chunk_place); start = starts[j].
+MCK_HOST_DEVICE_INLINE SegCopyAddr seg_copy_addr(int dir, uint64_t seg_at, uint64_t base, uint64_t start,
+                                                 uint64_t obj_off) {
+    const uint64_t flat = base + start + obj_off;
+    return dir == kSegGather ? SegCopyAddr{seg_at, flat} : SegCopyAddr{flat, seg_at};
+}
+
+}  // namespace mck
+
+#endif  // MCK_SEG_PLAN_H

@@ -38,6 +38,12 @@ SHAPES = {
     "c4_64": ("crc64", 262144, None, 0x4D43310000000004),
     "seg": ("crc64", 8192, "seg", 0x4D43310000000003),      # bench.py's segments layout
     "seg32": ("crc32c", 8192, "seg", 0x4D43310000000003),   # the same layout, CRC-32C
+    # gather_segments / scatter_segments, both methods each: on that layout, and on the ragged list of
+    # tools/ab_seg_copy.py (its pool and seed: 120 objects of 0..6 segments at arbitrary byte offsets)
+    "seg_gather": (("crc32c", "crc64"), 8192, "seg+gather", 0x4D43310000000003),
+    "seg_scatter": (("crc32c", "crc64"), 8192, "seg+scatter", 0x4D43310000000003),
+    "ragged_gather": (("crc32c", "crc64"), 120, "ragged+gather", 0x5E6),
+    "ragged_scatter": (("crc32c", "crc64"), 120, "ragged+scatter", 0x5E6),
     # small batches (per-call latency; the light layout up to 16 MiB)
     "s1": ("crc32c", 1, 4096, 0x4D43310000000002),
     "s64": ("crc32c", 64, 4096, 0x4D43310000000002),
@@ -67,7 +73,30 @@ def load(path):
                                                  c.c_void_p]
     L.mchecksum_gpu_checksum_segments.argtypes = [c.c_char_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
                                                   c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    if hasattr(L, "mchecksum_gpu_gather_segments"):
+        L.mchecksum_gpu_gather_segments.argtypes = [c.c_char_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t,
+                                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+        L.mchecksum_gpu_scatter_segments.argtypes = [c.c_char_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t,
+                                                     c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
     return L
+
+
+def ragged_segments(seed):
+    """The ragged list of tools/ab_seg_copy.py: segment lengths, byte offsets, objects' first segments, span."""
+    from ab_seg_copy import POOL
+    rng = np.random.default_rng(seed)
+    lens, first = [], [0]
+    for _ in range(120):
+        lens += [POOL[int(rng.integers(0, len(POOL)))] for _ in range(int(rng.integers(0, 7)))]
+        first.append(len(lens))
+    lens, first = np.asarray(lens, dtype=np.int64), np.asarray(first)
+    off = np.zeros(len(lens), dtype=np.int64)
+    at = 0
+    for i in rng.permutation(len(lens)):
+        at += int(rng.integers(0, 32))
+        off[i] = at
+        at += int(lens[i])
+    return lens, off, first, at
 
 
 def main():
@@ -104,20 +133,38 @@ def main():
         envs.append((var, val))
 
     results = {}
-    configs = args.config.split(",")
-    for cfg in configs:
-        method, count, length, seed = SHAPES[cfg]
-        offs = seg = None
-        if length == "seg":
-            from mercury_amd.workload import segment_slots
-            nbytes, slen = count << 20, (1 << 20) // 4
-            data = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+    runs = []  # a shape with several methods runs once per method, keyed shape/method
+    for cfg in args.config.split(","):
+        methods, count, length, seed = SHAPES[cfg]
+        runs += [(cfg, methods, count, length, seed)] if isinstance(methods, str) else \
+            [(f"{cfg}/{m}", m, count, length, seed) for m in methods]
+    for cfg, method, count, length, seed in runs:
+        offs = seg = flat = None
+        length, _, copy = length.partition("+") if isinstance(length, str) else (length, "", "")
+        if length in ("seg", "ragged"):
+            if length == "seg":
+                from mercury_amd.workload import segment_slots
+                nbytes, slen = count << 20, (1 << 20) // 4
+                data = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+                slots = segment_slots(seed, count * 4)
+                views, first = [data[int(q) * slen:(int(q) + 1) * slen] for q in slots], np.arange(0, count * 4 + 1, 4)
+                sizes = np.full(count, 1 << 20, dtype=np.int64)
+            else:
+                lens, off, first, span = ragged_segments(seed)
+                data = torch.empty(span + 128, dtype=torch.uint8, device="cuda")
+                views = [data[int(o):int(o) + int(n)] for o, n in zip(off, lens)]
+                P = np.concatenate([[0], np.cumsum(lens)])
+                sizes = P[first[1:]] - P[first[:-1]]
+                nbytes = int(sizes.sum())
             G.fill_splitmix(data, seed)
-            slots = segment_slots(seed, count * 4)
-            seg = G.SegmentBatch([data[int(q) * slen:(int(q) + 1) * slen] for q in slots],
-                                 np.arange(0, count * 4 + 1, 4))
+            seg = G.SegmentBatch(views, first)
             seg.work = torch.empty(2 * seg.work.numel() + (1 << 17), dtype=torch.int64, device="cuda")  # room for any variant
-            ref = seg.checksum(method)
+            if copy:  # the contiguous side: the objects back to back
+                flat = torch.empty(nbytes + 128, dtype=torch.uint8, device="cuda")
+                G.fill_splitmix(flat, seed + 1)
+                starts = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)).cuda()
+            ref = (seg.gather(method, flat, starts) if copy == "gather" else
+                   seg.scatter(method, flat, starts) if copy == "scatter" else seg.checksum(method))
         elif length is None:
             from mercury_amd.workload import varlen_offsets
             off_h = varlen_offsets(seed, count)
@@ -153,8 +200,16 @@ def main():
                         a.record(stream)
                     if seg is not None:
                         mb, ns = seg.meta.data_ptr(), seg.nseg
-                        rc = L.mchecksum_gpu_checksum_segments(method.encode(), mb, mb + 8 * ns, ns, mb + 16 * ns, seg.nobj,
-                                                               seg.work.data_ptr(), seg.work.numel() * 8, o.data_ptr(), h)
+                        tables = (mb, mb + 8 * ns, ns, mb + 16 * ns, seg.nobj)
+                        tail = (seg.work.data_ptr(), seg.work.numel() * 8, o.data_ptr(), h)
+                        if copy == "gather":
+                            rc = L.mchecksum_gpu_gather_segments(method.encode(), *tables, flat.data_ptr(), starts.data_ptr(),
+                                                                 *tail)
+                        elif copy == "scatter":
+                            rc = L.mchecksum_gpu_scatter_segments(method.encode(), flat.data_ptr(), starts.data_ptr(),
+                                                                  *tables, *tail)
+                        else:
+                            rc = L.mchecksum_gpu_checksum_segments(method.encode(), *tables, *tail)
                     elif offs is None:
                         d = copies[k % len(copies)]
                         rc = L.mchecksum_gpu_checksum_fixed(method.encode(), d.data_ptr(), length, length, count,
@@ -180,10 +235,15 @@ def main():
             t = np.array(times[n])
             res[n] = {"median_ms": float(np.median(t)), "min_ms": float(t.min()),
                       "GBs_median": nbytes / (np.median(t) * 1e-3) / 1e9, "GBs_best": nbytes / (t.min() * 1e-3) / 1e9}
+            rm = np.median(t.reshape(args.rounds, -1), axis=1)  # each round's median, and their spread
+            res[n].update(median_of_rounds_ms=float(np.median(rm)), round_min_ms=float(rm.min()),
+                          round_max_ms=float(rm.max()))
             print(f"{cfg:7s} {n:10s} median {res[n]['median_ms']:.4f} ms  min {res[n]['min_ms']:.4f} ms  "
-                  f"{res[n]['GBs_median']:.0f} GB/s (best {res[n]['GBs_best']:.0f})", flush=True)
+                  f"{res[n]['GBs_median']:.0f} GB/s (best {res[n]['GBs_best']:.0f})  rounds' medians "
+                  f"{res[n]['median_of_rounds_ms']:.4f} ({res[n]['round_min_ms']:.4f}..{res[n]['round_max_ms']:.4f}) ms",
+                  flush=True)
         results[cfg] = res
-        del data
+        del data, seg, flat
         copies = None
         torch.cuda.empty_cache()
     if args.out:
