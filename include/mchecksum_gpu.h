@@ -173,6 +173,21 @@ MCHECKSUM_PUBLIC int
 mchecksum_gpu_state_get(const char *hash_method, const void *dev_state,
     size_t count, void *dev_out, void *stream);
 
+/* state_get and the compare in one launch: dev_status[i] = 1 where the value
+ * state_get would return for dev_state[i] differs from dev_expected[i] (count
+ * host-order values of the method's size), else 0; *dev_mismatches (a device
+ * uint32_t the caller zeroes) is increased by the number of mismatches.
+ * Either of the two may be NULL.  The states are not modified.  No
+ * device-side wait, no work-queue slot and no workspace, like combine_runs,
+ * so nothing to fail closed on -- and no way to know whether an earlier
+ * update failed: check the error word first, as after update_offsets.
+ * Arguments as mchecksum_gpu_state_get (dev_expected required when
+ * count > 0).  Capture-safe. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_verify(const char *hash_method, const void *dev_state,
+    size_t count, const void *dev_expected, uint8_t *dev_status,
+    uint32_t *dev_mismatches, void *stream);
+
 /* dev_out[i] = CRC(A_i || B_i) from dev_crc_a[i] = CRC(A_i), dev_crc_b[i] =
  * CRC(B_i) -- finalized values as the checksum_* calls and state_get return
  * them -- and dev_len_b[i] = the bytes of B_i (< 2^48).  For chunks that
@@ -494,6 +509,93 @@ mchecksum_gpu_scatter_segments(const char *hash_method,
     const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
     const uint64_t *dev_obj_first, size_t nobj,
     void *dev_work, size_t work_size, void *dev_out, void *stream);
+
+/* Streaming over segment lists: a pipelined bulk transfer moves an object in
+ * stages, each stage a list of segments.  The three calls below are
+ * checksum_segments, gather_segments and scatter_segments with a running
+ * state in place of the output: dev_state[j] -- the opaque element of
+ * mchecksum_gpu_state_init / update_offsets / state_get, of the method's
+ * size -- is advanced over object j's segments, concatenated in order.  A
+ * state does not remember which call advanced it: offsets updates and
+ * segments updates mix in any order.
+ *
+ * Values.  state_init, any sequence of these updates, then state_get equals
+ * mchecksum_get() after mchecksum_update() over the same bytes in the same
+ * order, bit for bit, for every 32/64-bit catalogue method.  MSB-first
+ * methods included: states stay in the kernels' form, nothing is swapped.  An
+ * object with no bytes leaves its state unchanged and writes nothing.
+ *
+ * Everything else is the one-shot call's of the same shape: which bytes are
+ * written, the memory and overlap rules, the 2^40-segment cap, the workspace
+ * (mchecksum_gpu_segments_work_size(nseg), one per concurrent call), the
+ * work-queue and static-split rules.  An object's byte total in one call must
+ * be below 2^48 (the shift tables' range, as for combine_runs); larger totals
+ * read nothing out of range and leave an unspecified state.  Capture-safe
+ * after mchecksum_gpu_prepare(): a replay scans the tables again and advances
+ * the states again, seeded with that replay's byte totals.  One array of
+ * states must not be advanced by two calls at once.
+ *
+ * Failure.  As the one-shot calls: error word + 1 once per call and
+ * mchecksum_gpu_queue_faults().  A call whose scan gave up leaves every state
+ * as it was; after any other failed call the states are unspecified.  Check
+ * the error word before trusting them, as for update_offsets.
+ *
+ * Arguments are checked in checksum_segments' order: NULL pointers (dev_state
+ * is required when nobj > 0), the segment cap, the workspace, the device, the
+ * method.  nobj == 0 passes those checks and returns MCHECKSUM_GPU_OK.
+ *
+ * Cost.  One small launch more than the one-shot call (a thread per object
+ * seeds the states between the scan and the chunk pass); the chunk passes
+ * are the one-shot calls' kernels.  DESIGN.md 4.17 records what was and what
+ * was not measured. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_update_segments(const char *hash_method,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj, void *dev_work,
+    size_t work_size, void *dev_state, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_update_gather_segments(const char *hash_method,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj,
+    void *dev_dst, const uint64_t *dev_dst_starts,
+    void *dev_work, size_t work_size, void *dev_state, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_update_scatter_segments(const char *hash_method,
+    const void *dev_src, const uint64_t *dev_src_starts,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj,
+    void *dev_work, size_t work_size, void *dev_state, void *stream);
+
+/* checksum_segments with the compare on the device: dev_expected holds nobj
+ * host-order values of the method's size; dev_status[j] = 1 if the CRC of
+ * object j's segments differs from dev_expected[j], else 0, and
+ * *dev_mismatches (a device uint32_t the caller zeroes) is increased by the
+ * number of mismatches.  Either of the two may be NULL.  An object with no
+ * bytes is compared with the CRC of the empty message; MSB-first methods
+ * compare in the checksum calls' form.  Segment memory is never written.
+ * Tables, memory rules and the workspace (its size included) are
+ * checksum_segments'; the values are kept in the workspace, which is why the
+ * call takes fewer than 2^32 segments (more is MCHECKSUM_GPU_EINVAL, with the
+ * segment cap's rank) and why a list of more than 2 nseg + 65536 chunks of
+ * 256 KiB searches the scan's table per chunk instead of reading a map.
+ *
+ * Fail closed, as the verify calls: unhashed bytes never read as verified.
+ * A call whose scan or chunk pass gave up adds 1 to the error word, once, adds
+ * nobj to *dev_mismatches and sets every status to 1.  The compare runs after
+ * the chunk pass and reads the call's fault state first, so a value that is
+ * only half accumulated is never compared.
+ *
+ * Arguments are checked in checksum_segments' order, dev_expected required
+ * when nobj > 0; nobj == 0 returns MCHECKSUM_GPU_OK without a launch.
+ * Capture-safe after mchecksum_gpu_prepare(). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_segments(const char *hash_method,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj, void *dev_work,
+    size_t work_size, const void *dev_expected, uint8_t *dev_status,
+    uint32_t *dev_mismatches, void *stream);
 
 /* Batched check of Mercury core headers for received
  * messages in device memory: message i = dev_buf[dev_msg_offsets[i],

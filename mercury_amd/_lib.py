@@ -28,7 +28,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_update_offsets", "mchecksum_gpu_state_get", "mchecksum_gpu_combine",
                "mchecksum_gpu_seal_messages", "mchecksum_gpu_pack_messages", "mchecksum_gpu_seal_core_headers",
                "mchecksum_gpu_unpack_messages", "mchecksum_gpu_copy_offsets", "mchecksum_gpu_update_copy_offsets",
-               "mchecksum_gpu_gather_segments", "mchecksum_gpu_scatter_segments", "mchecksum_gpu_combine_runs")
+               "mchecksum_gpu_gather_segments", "mchecksum_gpu_scatter_segments", "mchecksum_gpu_combine_runs",
+               "mchecksum_gpu_update_segments", "mchecksum_gpu_update_gather_segments",
+               "mchecksum_gpu_update_scatter_segments", "mchecksum_gpu_verify_segments", "mchecksum_gpu_state_verify")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
@@ -92,6 +94,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_scatter_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                                  c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_scatter_segments.restype = c_int
+    # the streaming forms: the one-shot calls' arguments, a state array in place of the output
+    L.mchecksum_gpu_update_segments.argtypes = L.mchecksum_gpu_checksum_segments.argtypes
+    L.mchecksum_gpu_update_segments.restype = c_int
+    L.mchecksum_gpu_update_gather_segments.argtypes = L.mchecksum_gpu_gather_segments.argtypes
+    L.mchecksum_gpu_update_gather_segments.restype = c_int
+    L.mchecksum_gpu_update_scatter_segments.argtypes = L.mchecksum_gpu_scatter_segments.argtypes
+    L.mchecksum_gpu_update_scatter_segments.restype = c_int
+    # (method, seg_addr, seg_len, nseg, obj_first, nobj, work, work_size, expected, status, mismatches, stream)
+    L.mchecksum_gpu_verify_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_verify_segments.restype = c_int
     L.mchecksum_gpu_verify_core_headers.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                                     c_void_p, c_void_p]
     L.mchecksum_gpu_verify_core_headers.restype = c_int
@@ -112,6 +125,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_update_offsets.restype = c_int
     L.mchecksum_gpu_state_get.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_state_get.restype = c_int
+    # (method, state, count, expected, status, mismatches, stream)
+    L.mchecksum_gpu_state_verify.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_state_verify.restype = c_int
     L.mchecksum_gpu_combine.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_combine.restype = c_int
     # (method, crc, len, nchunks, run_first, nruns, out, out_len, stream)

@@ -76,6 +76,24 @@ mck_seed64(const crc64_shift_pack_t *sp, uint64_t x, uint64_t s, uint64_t init, 
     return x ^ mck_zshift64(sp, s ^ init, n);
 }
 
+/* The segment passes (mchecksum_gpu_ext.hip) XOR into an object's word what
+ * its chunks contribute: R(init, M) ^ init between them for an object of
+ * N > 0 bytes (the head chunk adds the init once more, seg_emit), nothing for
+ * one without bytes.  A segments update presets the word with the seed term
+ * so that it ends as R(s, M) -- s itself for N = 0, which the caller need not
+ * write: */
+MCK_HD uint32_t
+mck_seg_seed32(const crc32_shift_pack_t *sp, uint32_t s, uint32_t init, uint64_t n)
+{
+    return init ^ mck_zshift32(sp, s ^ init, n);
+}
+
+MCK_HD uint64_t
+mck_seg_seed64(const crc64_shift_pack_t *sp, uint64_t s, uint64_t init, uint64_t n)
+{
+    return init ^ mck_zshift64(sp, s ^ init, n);
+}
+
 /* Register <-> finalized value (what mchecksum_get() returns).  The kernels'
  * value of an MSB-first model is the CRC byte-swapped (crc_gpu_layout.h);
  * xorout is the model's in the kernels' domain (crc_rmodel_t). */
@@ -91,6 +109,20 @@ mck_reg_to_crc64(uint64_t r, uint64_t xorout, int msb)
 {
     r ^= xorout;
     return msb ? __builtin_bswap64(r) : r;
+}
+
+/* The finalized CRC of an object from x, the XOR of its chunks' contributions
+ * into a zeroed word (mck_seg_seed above): 0 for the empty message. */
+MCK_HD uint32_t
+mck_seg_value32(uint32_t x, uint32_t init, uint32_t xorout, int msb)
+{
+    return mck_reg_to_crc32(x ^ init, xorout, msb);
+}
+
+MCK_HD uint64_t
+mck_seg_value64(uint64_t x, uint64_t init, uint64_t xorout, int msb)
+{
+    return mck_reg_to_crc64(x ^ init, xorout, msb);
 }
 
 MCK_HD uint32_t

@@ -57,6 +57,7 @@
 #include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
+#include "seg_plan.h"
 
 namespace mck {
 // ------------------------------------------------------------ host side ----
@@ -559,6 +560,22 @@ __global__ __launch_bounds__(256) void state_get_kernel(const T *st, T *out, uin
     }
 }
 
+// state_get and the compare in one launch (seg_plan.h: seg_verify_decide, the
+// verdict verify_segments writes; no fault state to read here).  The states
+// are only read.
+template <typename T>
+__global__ __launch_bounds__(256) void state_verify_kernel(const T *st, const T *expected, uint64_t n, T xorout, int msb,
+                                                           uint8_t *status, uint32_t *mism) {
+    uint32_t nbad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        uint64_t v;
+        if constexpr (sizeof(T) == 8) v = mck_reg_to_crc64(st[i], xorout, msb);
+        else v = mck_reg_to_crc32(st[i], xorout, msb);
+        nbad += mck::seg_verify_decide(false, v, expected[i], status, i);
+    }
+    add_mismatches(mism, nbad);  // once per workgroup (crc_gpu_common.h)
+}
+
 // out may alias a or b, element for element
 template <typename T>
 __global__ __launch_bounds__(256) void combine_kernel(const T *a, const T *b, const uint64_t *len_b, T *out, uint64_t n,
@@ -998,6 +1015,26 @@ int mchecksum_gpu_state_get(const char *hash_method, const void *dev_state, size
                                       (const uint32_t *)dev_state, (uint32_t *)dev_out, (uint64_t)count,
                                       (uint32_t)rm.xorout, rm.msb);
     return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "state get");
+}
+
+int mchecksum_gpu_state_verify(const char *hash_method, const void *dev_state, size_t count, const void *dev_expected,
+                               uint8_t *dev_status, uint32_t *dev_mismatches, void *stream) {
+    if (count && (!dev_state || !dev_expected)) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    Model m;
+    crc_rmodel_t rm;
+    DevCtx *c = nullptr;
+    if (int rc = state_call(hash_method, count, &m, &rm, &c)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    // no work-queue slot, no workspace, no device-side wait: nothing to fail closed on
+    const dim3 grid(elem_grid(count)), block(256);
+    const hipError_t e =
+        m.width == 64 ? launch_kernel(state_verify_kernel<uint64_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint64_t *)dev_state, (const uint64_t *)dev_expected, (uint64_t)count,
+                                      (uint64_t)rm.xorout, rm.msb, dev_status, dev_mismatches)
+                      : launch_kernel(state_verify_kernel<uint32_t>, grid, block, (hipStream_t)stream, nullptr,
+                                      (const uint32_t *)dev_state, (const uint32_t *)dev_expected, (uint64_t)count,
+                                      (uint32_t)rm.xorout, rm.msb, dev_status, dev_mismatches);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "state verify");
 }
 
 int mchecksum_gpu_combine(const char *hash_method, const void *dev_crc_a, const void *dev_crc_b,

@@ -348,8 +348,10 @@ __device__ __forceinline__ void scan_block(const ScanArgs &sa, uint64_t b, uint6
     uint32_t *row_ne = reinterpret_cast<uint32_t *>(row_hs + kScanBlk);  // 1: the segment is not empty
     uint64_t *bc = reinterpret_cast<uint64_t *>(row_ne + kScanBlk);     // jb, je, ex[3]
     uint32_t *rag = reinterpret_cast<uint32_t *>(bc + 5);
-    // every object starts as the CRC of the empty message (the chunk passes XOR into it)
-    if (act)
+    // every object starts as the CRC of the empty message (the chunk passes XOR
+    // into it); an update or verify call (no out here) presets its words after
+    // the scan, when the objects' byte totals are known (seg_pre_kernel)
+    if (act && sa.out)
         for (uint64_t j = b * kScanThreads + tid; j < nobj; j += nb * kScanThreads) {
             if (sa.width == 64) reinterpret_cast<uint64_t *>(sa.out)[j] = sa.preset;
             else reinterpret_cast<uint32_t *>(sa.out)[j] = (uint32_t)sa.preset;
@@ -600,8 +602,19 @@ __device__ __forceinline__ void seg_emit(const Pack *pk, const Shift *sp, void *
 // 0's scan with an agent-scope acquire -- and not kept: HISTORY.md.)
 constexpr uint64_t kSegNtBytes = 512ull << 20;
 
-template <int W>
-__global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
+// verify_segments' pass (BYSEG) has no output array: the object's word lies
+// in the workspace, indexed by the object's first segment (seg_plan.h,
+// seg_verify_layout).  false: no such segment -- skip the chunk.
+__device__ __forceinline__ bool seg_by_first(const SegArgs &a, SegChunk *k) {
+    const uint64_t fs = a.first[k->obj];
+    k->obj = fs;
+    return mck::seg_segment_ok(fs, a.nseg);
+}
+
+// The pass itself; BYSEG also leaves the call's key in *chunk_claim when a
+// wait of the work queue gave up, for the compare that follows.
+template <int W, bool BYSEG>
+__device__ __forceinline__ void seg_pass(const SegArgs &a, uint64_t *chunk_claim) {
     __shared__ __attribute__((aligned(16))) uint8_t lds_tab[W == 32 ? kL32Bytes : kL64Bytes];
     constexpr int kWPB = 1024 / 64;
     const uint32_t lane = threadIdx.x & 63u;
@@ -630,6 +643,8 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         SegChunk k;
         while (walk.next(&k)) {
             if (!k.in) continue;
+            if constexpr (BYSEG)
+                if (!seg_by_first(a, &k)) continue;
             const uint8_t *q = reinterpret_cast<const uint8_t *>(k.addr);
             const uint64_t n = k.n;
             // whole rings of 1 KiB steps from a 16-B aligned start (the usual
@@ -668,6 +683,8 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         };
         auto locate = [&](uint64_t c, Chunk *k) {
             seg_locate<false>(a, c, nchunks, k);
+            if constexpr (BYSEG)
+                if (k->in) k->in = seg_by_first(a, k);
             k->even = k->in && k->addr % 16 == 0 && k->n % (1024u * kRing64) == 0 && k->n >= 2048u * kRing64;
         };
         auto issue = [&](uint4 (&ring)[kRing64], const Chunk &k) {
@@ -717,7 +734,89 @@ __global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
         }
         const bool faulted = tk.finish(wave);
         if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
+        if constexpr (BYSEG)
+            if (faulted && lane == 0) st_relaxed(chunk_claim, scan_key(a.epoch, ld_relaxed(a.w.gen) - 1));
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(1024, 1) void seg_kernel(SegArgs a) {
+    seg_pass<W, false>(a, nullptr);
+}
+
+// verify_segments: the chunk pass into the workspace's words, then the compare.
+struct SegVerifyArgs {
+    SegArgs s;  // s.out: the accumulator words (seg_verify_layout)
+    uint64_t *chunk_claim;
+    const void *expected;
+    uint8_t *status;
+    uint32_t *mism;
+    uint64_t init, xorout;
+    int msb;
+};
+
+template <int W>
+__global__ __launch_bounds__(1024, 1) void seg_verify_pass_kernel(SegVerifyArgs va) {
+    seg_pass<W, true>(va.s, va.chunk_claim);
+}
+
+// Between the scan and the chunk pass of an update or verify call, a thread
+// per object.  Update: the state becomes the seed term of the object's byte
+// total (crc_gpu_seed.h, mck_seg_seed), so that the chunk pass's XORs end it
+// as R(s, M); an object without bytes is not written, and after a scan that
+// gave up neither is any (the chunk pass then hashes nothing: the states
+// stay as they were).  Verify (SEED false): the object's word starts at 0.
+struct SegPreArgs {
+    const uint64_t *first;
+    uint64_t nobj, nseg, epoch;
+    SegWork w;
+    void *word;  // the states, or verify's accumulator words
+    const void *shift;
+    uint64_t init;
+};
+
+template <typename T, bool SEED>
+__global__ __launch_bounds__(256) void seg_pre_kernel(SegPreArgs a) {
+    if constexpr (SEED)
+        if (ld_relaxed(a.w.fault_claim) == scan_key(a.epoch, ld_relaxed(a.w.gen) - 1)) return;
+    T *word = reinterpret_cast<T *>(a.word);
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < a.nobj; j += (uint64_t)gridDim.x * 256) {
+        const uint64_t f0 = a.first[j], f1 = a.first[j + 1];
+        if (!(f0 < f1 && f1 <= a.nseg)) continue;
+        if constexpr (!SEED) {
+            word[f0] = 0;
+        } else {
+            const uint64_t n = a.w.P[f1] - a.w.P[f0];
+            if (n == 0) continue;
+            if constexpr (sizeof(T) == 8)
+                word[j] = mck_seg_seed64(reinterpret_cast<const crc64_shift_pack_t *>(a.shift), word[j], a.init, n);
+            else
+                word[j] = mck_seg_seed32(reinterpret_cast<const crc32_shift_pack_t *>(a.shift), word[j],
+                                         (uint32_t)a.init, n);
+        }
+    }
+}
+
+// verify_segments' compare, after the chunk pass: the call's fault state
+// first, then a thread per object (seg_plan.h: seg_call_faulted,
+// seg_verify_decide).  An object without segments has no word: its value is
+// the CRC of the empty message, as is that of one whose segments are empty.
+template <typename T>
+__global__ __launch_bounds__(256) void seg_verify_kernel(SegVerifyArgs va) {
+    const SegArgs &a = va.s;
+    const bool faulted = mck::seg_call_faulted(ld_relaxed(a.w.fault_claim), ld_relaxed(va.chunk_claim),
+                                               scan_key(a.epoch, ld_relaxed(a.w.gen) - 1));
+    const T *acc = reinterpret_cast<const T *>(a.out);
+    uint32_t nbad = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < a.nobj; j += (uint64_t)gridDim.x * 256) {
+        const uint64_t f0 = a.first[j], f1 = a.first[j + 1];
+        const T x = !faulted && f0 < f1 && f1 <= a.nseg ? acc[f0] : (T)0;
+        uint64_t v;
+        if constexpr (sizeof(T) == 8) v = mck_seg_value64(x, va.init, va.xorout, va.msb);
+        else v = mck_seg_value32(x, (uint32_t)va.init, (uint32_t)va.xorout, va.msb);
+        nbad += mck::seg_verify_decide(faulted, v, reinterpret_cast<const T *>(va.expected)[j], va.status, j);
+    }
+    add_mismatches(va.mism, nbad);  // once per workgroup (crc_gpu_common.h); no counter: nothing added
 }
 
 // The copying chunk passes (mchecksum_gpu_gather_segments, _scatter_segments):
@@ -1182,6 +1281,12 @@ uint64_t scan_epoch() {
 // (the workspace's layout: seg_work_layout, seg_plan.h)
 size_t mchecksum_gpu_segments_work_size(size_t nseg) { return seg_work_bytes(nseg); }
 
+// grid of the per-object launches of an update or verify call (256 threads)
+static unsigned seg_elem_grid(uint64_t n) {
+    const uint64_t blocks = (n + 255) / 256;
+    return blocks > 1024 ? 1024u : (unsigned)blocks;
+}
+
 // One segment call: checksum_segments, or with a direction (mck::kSegGather /
 // kSegScatter), the contiguous side and its starts table, a copying call.
 constexpr int kSegHashOnly = -1;
@@ -1198,18 +1303,30 @@ struct SegCall {
     int dir = kSegHashOnly;
     void *flat = nullptr;              // gather: the destination; scatter: the source
     const uint64_t *starts = nullptr;  // nobj byte offsets into it
+    // what becomes of the objects' registers: values in out; running states in
+    // out advanced in place (the update calls); or compared on the device with
+    // expected (verify_segments: no out)
+    enum Mode { kValues, kUpdate, kVerify } mode = kValues;
+    const void *expected = nullptr;
+    uint8_t *status = nullptr;
+    uint32_t *mism = nullptr;
 };
 
-// The front of the three segment entry points: the argument checks, the scan
-// launch and the chunk pass -- seg_kernel, or for a copying call
-// seg_copy_kernel under the same launch policy.
+// The front of the segment entry points: the argument checks, the scan launch
+// and the chunk pass -- seg_kernel, or for a copying call seg_copy_kernel
+// under the same launch policy.  An update call seeds the states between the
+// two (seg_pre_kernel) and has the same chunk pass XOR into them; verify runs
+// the chunk pass on words of the workspace and the compare after it.
 static int seg_call(const SegCall &sc) {
-    const bool copy = sc.dir != kSegHashOnly;
+    const bool copy = sc.dir != kSegHashOnly, verify = sc.mode == SegCall::kVerify;
     const size_t nseg = sc.nseg, nobj = sc.nobj;
-    if (!sc.obj_first || (nobj && !sc.out) || (nseg && (!sc.seg_addr || !sc.seg_len)) || !sc.work ||
-        (copy && nobj && (!sc.flat || !sc.starts)))
+    if (!sc.obj_first || (nobj && !(verify ? sc.expected : sc.out)) || (nseg && (!sc.seg_addr || !sc.seg_len)) ||
+        !sc.work || (copy && nobj && (!sc.flat || !sc.starts)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if ((uint64_t)nseg > kMaxSegs) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^40 segments in one call");
+    mck::SegVerifyLayout vl{};
+    if (verify && !mck::seg_verify_layout(nseg, &vl))
+        return set_err(MCHECKSUM_GPU_EINVAL, "verify_segments takes fewer than 2^32 segments in one call");
     if (sc.work_size < mchecksum_gpu_segments_work_size(nseg) || (uintptr_t)sc.work % 8)
         return set_err(MCHECKSUM_GPU_EINVAL, "workspace smaller than mchecksum_gpu_segments_work_size() or unaligned");
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
@@ -1232,9 +1349,11 @@ static int seg_call(const SegCall &sc) {
     a.w = seg_work(sc.work, nseg);
     // only the CRC-64 queue pass reads the map; MCHECKSUM_GPU_SEG_MAP_CAP caps
     // the part of it used (tests: 0 forces the search over C)
-    const uint64_t cap = width == 64 ? a.w.map_cap : 0, v = mck_settings()->gpu_seg_map_cap;
+    // (verify keeps its words in the map's tail: seg_verify_layout)
+    const uint64_t cap = width == 64 ? (verify ? vl.map_cap : a.w.map_cap) : 0, v = mck_settings()->gpu_seg_map_cap;
     a.w.map_cap = v < cap ? v : cap;
-    a.out = sc.out;
+    uint64_t *const work = static_cast<uint64_t *>(sc.work);
+    a.out = verify ? static_cast<void *>(work + vl.acc) : sc.out;
     a.pack = pack;
     a.shift = shift;
     a.err_word = error_word();
@@ -1252,7 +1371,7 @@ static int seg_call(const SegCall &sc) {
     sa.nobj = nobj;
     sa.w = a.w;
     if (width != 64) sa.w.obj = nullptr;  // only the queue pass reads the object records
-    sa.out = sc.out;
+    sa.out = sc.mode == SegCall::kValues ? sc.out : nullptr;  // (the others: seg_pre_kernel, after the scan)
     sa.width = (uint32_t)width;
     sa.preset = rm.rinit ^ rm.xorout;
     sa.err_word = a.err_word;
@@ -1260,9 +1379,25 @@ static int seg_call(const SegCall &sc) {
     hipError_t e = launch_kernel(seg_scan, dim3((unsigned)seg_scan_blocks(nseg)), dim3(kScanThreads),
                                  (hipStream_t)sc.stream, nullptr, sa);
     if (e != hipSuccess) return hip_err(e, "segment scan launch");
+    if (sc.mode != SegCall::kValues) {
+        const SegPreArgs pa{sc.obj_first, nobj, nseg, a.epoch, a.w, a.out, shift, rm.rinit};
+        auto k = verify ? (width == 32 ? seg_pre_kernel<uint32_t, false> : seg_pre_kernel<uint64_t, false>)
+                        : (width == 32 ? seg_pre_kernel<uint32_t, true> : seg_pre_kernel<uint64_t, true>);
+        e = launch_kernel(k, dim3(seg_elem_grid(nobj)), dim3(256), (hipStream_t)sc.stream, nullptr, pa);
+        if (e != hipSuccess) return hip_err(e, "segment seed launch");
+    }
     SlotRef sr;  // only the CRC-64 pass takes chunks from a work queue
     if (width == 64) sr = queue_slot(c, sc.stream);
     a.queue = sr.q;
+    if (verify) {
+        const SegVerifyArgs va{a, work + vl.chunk_claim, sc.expected, sc.status, sc.mism, rm.rinit, rm.xorout, rm.msb};
+        rc = launch_slot(c, sr, width == 32 ? seg_verify_pass_kernel<32> : seg_verify_pass_kernel<64>, (unsigned)c->cus,
+                         1024, sc.stream, va, "segment kernel launch");
+        if (rc != MCHECKSUM_GPU_OK) return rc;
+        e = launch_kernel(width == 32 ? seg_verify_kernel<uint32_t> : seg_verify_kernel<uint64_t>,
+                          dim3(seg_elem_grid(nobj)), dim3(256), (hipStream_t)sc.stream, nullptr, va);
+        return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "segment verify launch");
+    }
     if (!copy) {
         rc = launch_slot(c, sr, width == 32 ? seg_kernel<32> : seg_kernel<64>, (unsigned)c->cus, 1024, sc.stream, a,
                          "segment kernel launch");
@@ -1273,8 +1408,9 @@ static int seg_call(const SegCall &sc) {
                              : (gather ? seg_copy_kernel<64, mck::kSegGather> : seg_copy_kernel<64, mck::kSegScatter>);
         rc = launch_slot(c, sr, k, (unsigned)c->cus, 1024, sc.stream, ca, "segment copy kernel launch");
     }
-    // MSB-first model: the kernels' values are the CRCs byte-swapped (crc_gpu_layout.h)
-    if (rc == MCHECKSUM_GPU_OK && m.msb) rc = swap_outputs(sc.out, nobj, width, sc.stream);
+    // MSB-first model: the kernels' values are the CRCs byte-swapped
+    // (crc_gpu_layout.h); running registers stay in the kernels' form
+    if (rc == MCHECKSUM_GPU_OK && m.msb && sc.mode == SegCall::kValues) rc = swap_outputs(sc.out, nobj, width, sc.stream);
     return rc;
 }
 
@@ -1304,6 +1440,50 @@ int mchecksum_gpu_scatter_segments(const char *hash_method, const void *dev_src,
     sc.dir = mck::kSegScatter;
     sc.flat = const_cast<void *>(dev_src);
     sc.starts = dev_src_starts;
+    return seg_call(sc);
+}
+
+int mchecksum_gpu_update_segments(const char *hash_method, const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len,
+                                  size_t nseg, const uint64_t *dev_obj_first, size_t nobj, void *dev_work,
+                                  size_t work_size, void *dev_state, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_state, stream};
+    sc.mode = SegCall::kUpdate;
+    return seg_call(sc);
+}
+
+int mchecksum_gpu_update_gather_segments(const char *hash_method, const uint64_t *dev_seg_addr,
+                                         const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
+                                         size_t nobj, void *dev_dst, const uint64_t *dev_dst_starts, void *dev_work,
+                                         size_t work_size, void *dev_state, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_state, stream};
+    sc.dir = mck::kSegGather;
+    sc.flat = dev_dst;
+    sc.starts = dev_dst_starts;
+    sc.mode = SegCall::kUpdate;
+    return seg_call(sc);
+}
+
+int mchecksum_gpu_update_scatter_segments(const char *hash_method, const void *dev_src, const uint64_t *dev_src_starts,
+                                          const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+                                          const uint64_t *dev_obj_first, size_t nobj, void *dev_work, size_t work_size,
+                                          void *dev_state, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, dev_state, stream};
+    sc.dir = mck::kSegScatter;
+    sc.flat = const_cast<void *>(dev_src);
+    sc.starts = dev_src_starts;
+    sc.mode = SegCall::kUpdate;
+    return seg_call(sc);
+}
+
+int mchecksum_gpu_verify_segments(const char *hash_method, const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len,
+                                  size_t nseg, const uint64_t *dev_obj_first, size_t nobj, void *dev_work,
+                                  size_t work_size, const void *dev_expected, uint8_t *dev_status,
+                                  uint32_t *dev_mismatches, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, nullptr, stream};
+    sc.mode = SegCall::kVerify;
+    sc.expected = dev_expected;
+    sc.status = dev_status;
+    sc.mism = dev_mismatches;
     return seg_call(sc);
 }
 

@@ -98,6 +98,31 @@ MCK_HOST_DEVICE_INLINE size_t seg_work_bytes(uint64_t nseg) {
     return nseg > kMaxSegs ? SIZE_MAX : (size_t)seg_work_layout(nseg).bytes;
 }
 
+// verify_segments has no output array, so the chunk pass accumulates in the
+// workspace: a word per object that has segments, indexed by the object's
+// first segment (distinct among such objects, below nseg; an object without
+// segments has no chunk and needs no word).  The words are the tail of the
+// map's region -- the call uses a map of 2 nseg + 64 Ki entries instead of 4
+// nseg + 64 Ki, and a list with more chunks than that searches C, as any list
+// past the map does -- so the workspace keeps its size.  From 2^32 segments on
+// there is no map to take them from: such a call is refused.  The chunk pass
+// leaves its own fault claim in the spare word, as the scan leaves its in
+// fault_claim: the call's key when a wait of that pass gave up.
+constexpr uint64_t kMaxVerifySegs = (1ull << 32) - 1;
+struct SegVerifyLayout {
+    uint64_t acc;      // 8-byte word offset of the nseg accumulator words
+    uint64_t map_cap;  // map entries left to the call
+    uint64_t chunk_claim;
+};
+MCK_HOST_DEVICE_INLINE bool seg_verify_layout(uint64_t nseg, SegVerifyLayout *v) {
+    const SegWorkLayout w = seg_work_layout(nseg);
+    if (nseg > kMaxVerifySegs || w.map_cap < 2 * nseg) return false;
+    v->map_cap = w.map_cap - 2 * nseg;
+    v->acc = w.map + v->map_cap / 2;  // (map_cap is even: the words stay 8-byte aligned)
+    v->chunk_claim = w.spare;
+    return true;
+}
+
 // The workspace's regions as pointers, shared by the scan (which writes them
 // through its own writable view) and the chunk passes (which only read).
 template <class U64, class U32>
@@ -190,6 +215,26 @@ MCK_HOST_DEVICE_INLINE SegCopyAddr seg_copy_addr(int dir, uint64_t seg_at, uint6
                                                  uint64_t obj_off) {
     const uint64_t flat = base + start + obj_off;
     return dir == kSegGather ? SegCopyAddr{seg_at, flat} : SegCopyAddr{flat, seg_at};
+}
+
+// verify_segments fails closed.  Its compare runs after the chunk pass and
+// first reads the call's fault state from the workspace: the scan's claim
+// and the chunk pass's, each equal to the call's key when that stage gave up.
+MCK_HOST_DEVICE_INLINE bool seg_call_faulted(uint64_t scan_claim, uint64_t chunk_claim, uint64_t key) {
+    return scan_claim == key || chunk_claim == key;
+}
+// What the compare writes for object j: after a faulted call status 1 whatever
+// the value holds (it may be half accumulated), otherwise whether the value
+// differs from the expected one.  Returns what j adds to the mismatch counter
+// (the caller sums it and adds the sum where there is a counter), so a faulted
+// call adds nobj between its objects.  status may be NULL.  state_verify
+// decides with the same function: it has no fault state to read (faulted =
+// false).
+MCK_HOST_DEVICE_INLINE uint32_t seg_verify_decide(bool faulted, uint64_t value, uint64_t expected, uint8_t *status,
+                                                  uint64_t j) {
+    const uint32_t bad = faulted || value != expected ? 1u : 0u;
+    if (status) status[j] = (uint8_t)bad;
+    return bad;
 }
 
 }  // namespace mck

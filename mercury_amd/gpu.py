@@ -320,6 +320,51 @@ def state_get(method: str, state: torch.Tensor, out: torch.Tensor | None = None,
     return out
 
 
+def _verdict_buffers(count: int, device, status, mismatches):
+    """The status / counter pair of a verify call: None allocates (status
+    starts "failed", the counter at zero), False passes NULL to the library, a
+    tensor is used as it is (the call adds to a counter the caller zeroed)."""
+    if status is None:
+        status = torch.ones(max(count, 0), dtype=torch.uint8, device=device)
+    elif status is not False and (not isinstance(status, torch.Tensor) or status.dtype != torch.uint8
+                                  or status.numel() < count or not status.is_cuda or not status.is_contiguous()):
+        raise GpuChecksumError("status must be a contiguous device uint8 tensor of at least count elements")
+    if mismatches is None:
+        mismatches = torch.zeros(1, dtype=torch.int32, device=device)
+    elif mismatches is not False and (not isinstance(mismatches, torch.Tensor) or mismatches.dtype != torch.int32
+                                      or not mismatches.is_cuda or mismatches.numel() < 1):
+        raise GpuChecksumError("mismatches must be a device int32 tensor")
+    for name, t in (("status", status), ("mismatches", mismatches)):
+        if t is not False and t.device != device:
+            raise GpuChecksumError(f"{name} must be on {device}")
+    return status, mismatches
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not False else None
+
+
+def state_verify(method: str, state: torch.Tensor, expected: torch.Tensor, status=None, mismatches=None,
+                 stream=None):
+    """state_get and the compare in one launch (mchecksum_gpu_state_verify):
+    returns (status uint8 per stream: 1 = the stream's CRC so far differs from
+    expected[i], mismatch count tensor).  status / mismatches: None allocates,
+    False leaves that output out, a tensor is reused (the count is added to).
+    The states are left as they are.  It cannot know whether an earlier update
+    failed: check the error word first."""
+    count = state.numel() if isinstance(state, torch.Tensor) else 0
+    _check_state(state, method, count, "state")
+    _check_state(expected, method, count, "expected")
+    _same_device(state, expected=expected)
+    status, mism = _verdict_buffers(count, state.device, status, mismatches)
+    with _on(state):
+        rc = _lib().mchecksum_gpu_state_verify(method.encode(), state.data_ptr(), count, expected.data_ptr(),
+                                               _ptr(status), _ptr(mism), _stream_handle(stream, state.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_verify")
+    return status, mism
+
+
 def combine(method: str, crc_a: torch.Tensor, crc_b: torch.Tensor, len_b: torch.Tensor,
             out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
     """CRC(A_i || B_i) from crc_a[i] = CRC(A_i), crc_b[i] = CRC(B_i) and
@@ -757,6 +802,76 @@ class SegmentBatch:
                                                                   out.data_ptr(), h))
         self._starts = st
         return out
+
+    def _state(self, method: str, state):
+        _check_state(state, method, self.nobj, "state")
+        if state.device != self.device:
+            raise GpuChecksumError(f"state must be on {self.device}")
+        return state
+
+    def update(self, method: str, state: torch.Tensor, stream=None) -> torch.Tensor:
+        """checksum as one stage of a stream: state[j] (state_init's element,
+        the one update_offsets advances) is advanced in place over object j's
+        segments in order, their current lengths; an object with no bytes
+        keeps its state.  Read the values with state_get or compare them with
+        state_verify.  Returns state."""
+        state = self._state(method, state)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_update_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_update_segments(method.encode(), base, base + 8 * n, n, base + 16 * n,
+                                                                 self.nobj, self.work.data_ptr(),
+                                                                 self.work.numel() * 8, state.data_ptr(), h))
+        return state
+
+    def update_gather(self, method: str, dst: torch.Tensor, dst_starts, state: torch.Tensor, stream=None,
+                      dst_starts_host=None) -> torch.Tensor:
+        """gather as one stage of a stream: the bytes go where gather puts
+        them (its rules and host checks) and state[j] is advanced over them.
+        Returns state."""
+        st = self._flat(dst, dst_starts, dst_starts_host, "dst")
+        state = self._state(method, state)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_update_gather_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_update_gather_segments(method.encode(), base, base + 8 * n, n,
+                                                                        base + 16 * n, self.nobj, dst.data_ptr(),
+                                                                        st.data_ptr(), self.work.data_ptr(),
+                                                                        self.work.numel() * 8, state.data_ptr(), h))
+        self._starts = st
+        return state
+
+    def update_scatter(self, method: str, src: torch.Tensor, src_starts, state: torch.Tensor, stream=None,
+                       src_starts_host=None) -> torch.Tensor:
+        """scatter as one stage of a stream (scatter's rules and host checks):
+        the segment tensors are written and state[j] is advanced over object
+        j's bytes.  Returns state."""
+        st = self._flat(src, src_starts, src_starts_host, "src")
+        state = self._state(method, state)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_update_scatter_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_update_scatter_segments(method.encode(), src.data_ptr(), st.data_ptr(),
+                                                                         base, base + 8 * n, n, base + 16 * n,
+                                                                         self.nobj, self.work.data_ptr(),
+                                                                         self.work.numel() * 8, state.data_ptr(), h))
+        self._starts = st
+        return state
+
+    def verify(self, method: str, expected: torch.Tensor, status=None, mismatches=None, stream=None):
+        """checksum with the compare on the device: returns (status uint8 per
+        object: 1 = its CRC differs from expected[j], mismatch count tensor).
+        status / mismatches: None allocates, False leaves that output out, a
+        tensor is reused (the count is added to).  Fails closed: a call that
+        could not hash every byte flags every object and adds nobj."""
+        _check_state(expected, method, self.nobj, "expected")
+        if expected.device != self.device:
+            raise GpuChecksumError(f"expected must be on {self.device}")
+        status, mism = _verdict_buffers(self.nobj, self.device, status, mismatches)
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_verify_segments", stream,
+                  lambda h: _lib().mchecksum_gpu_verify_segments(method.encode(), base, base + 8 * n, n, base + 16 * n,
+                                                                 self.nobj, self.work.data_ptr(),
+                                                                 self.work.numel() * 8, expected.data_ptr(),
+                                                                 _ptr(status), _ptr(mism), h))
+        return status, mism
 
 
 def _check_segment_tables(flat_bytes: int, flat_addr: int, starts, seg_addr, seg_lens, first) -> None:
