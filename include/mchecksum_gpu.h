@@ -672,6 +672,68 @@ mchecksum_gpu_checksum_xdr(const char *hash_method,
     const uint64_t *dev_msg_offsets, size_t count, void *dev_out,
     uint8_t *dev_status, void *stream);
 
+/* XDR-mode messages in place: the three calls a non-XDR build makes with
+ * mchecksum_gpu_verify_messages, _seal_messages and _unpack_messages, for a
+ * Mercury built with MERCURY_USE_XDR.  Message i = dev_buf[dev_msg_offsets[i],
+ * dev_msg_offsets[i+1]); its proc buffer -- what mchecksum_gpu_checksum_xdr
+ * calls the message -- starts payload_offset bytes in, and the header hash is
+ * the network-order u32 at hash_offset, hash_offset + 4 <= payload_offset
+ * (Mercury: 20 and 16).  fields / nfields: checksum_xdr's schema, with its
+ * rules; bytes after the schema's end are ignored (slices of a multi-recv
+ * buffer carry slack).  The header slot is 32 bits: reflected 32-bit methods
+ * only (crc32c, crc32); every other method gives MCHECKSUM_GPU_EMETHOD.
+ * Arguments are checked in this order: MCHECKSUM_GPU_EINVAL (NULL pointers,
+ * the offsets rule, a bad schema, count > 2^31), then the method, then the
+ * device; count == 0 needs no buffers and passes the same checks.
+ *
+ * verify: dev_status[i] = 1 when the message is shorter than payload_offset,
+ *   the schema runs past it, or the value checksum_xdr would return differs
+ *   from the header hash; else 0.  *dev_mismatches (zeroed by the caller) is
+ *   increased by the number of failures.  Either may be NULL.  dev_buf is
+ *   not written.
+ * seal: the value is stored big-endian in the 4 hash bytes, dev_status[i] =
+ *   0; a short or truncated message gets status 1 and is not written.  No
+ *   other byte is written.
+ * unpack: verify, and in the same pass the hashed stream -- the little-endian
+ *   `size` bytes of every INT, the unpadded bytes of every OPAQUE and RAW
+ *   field, in schema order: the message's non-XDR image -- is written to
+ *   dev_dst[dev_dst_offsets[i], dev_dst_offsets[i+1]) (count + 1 entries).  A
+ *   message fits when its decoded length, which depends on its data, equals
+ *   its slot's length; one that is short, truncated or does not fit gets
+ *   status 1, one mismatch and no destination byte written.  A fitting
+ *   message whose CRC differs gets status 1, one mismatch, and its slot holds
+ *   the bytes as decoded: look at the status before the bytes.  Exactly the
+ *   destination bytes of fitting messages are written.  dev_buf is not
+ *   written; the two ranges must not overlap.
+ *
+ * Launch, work-queue slot and graph capture as checksum_xdr (capture-safe
+ * after mchecksum_gpu_prepare(); a replay reads the buffer's current
+ * contents).  Fail closed: a call whose throughput layout gave up a wait adds
+ * 1 to the error word, adds count to *dev_mismatches and sets every status to
+ * 1; hash slots (seal) and destination bytes (unpack) of messages it cannot
+ * vouch for are unspecified.  (Statuses are flagged by a short launch after
+ * the walk, made only by calls that hold a work-queue slot and pass
+ * dev_status.) */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_xdr_messages(const char *hash_method,
+    const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, uint32_t *dev_mismatches,
+    void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_xdr_messages(const char *hash_method,
+    const mchecksum_xdr_field_t *fields, size_t nfields, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_xdr_messages(const char *hash_method,
+    const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+    uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
+
 /* Lanes cooperating on one payload that checksum_fixed would choose for
  * this length (1..64) in a batch large enough to fill the device; a smaller
  * batch gets more lanes per payload until it fills every wave slot (a small

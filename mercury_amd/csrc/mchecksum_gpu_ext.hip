@@ -1066,19 +1066,108 @@ __device__ __forceinline__ xdr_reg_t<W> xdr_tab_entry(uint64_t rpoly, uint32_t t
     return r;
 }
 
-// One message (one wave, wave-uniform walk): writes out[m] and status[m].
-// fast(p, len, &L) may hash an opaque/raw field of len bytes at p itself,
-// continuing the running register L (returning true); otherwise 64 lane
-// ranges are hashed byte by byte and combined into L.
-template <int W, class Fast>
-__device__ __forceinline__ void xdr_message(const XdrArgs &a, uint64_t m, const xdr_reg_t<W> *tab, uint32_t lane,
-                                            Fast &&fast) {
+// What an XDR call does with each message's value x (as launch_plan.h's
+// BatchOp names the offsets kernels' operations: the one name an entry point
+// gives its call, carried into the kernels' OP template argument, from which
+// the walk derives its compile-time variants -- so checksum_xdr's kernels are
+// the code they were).  The three message operations take whole messages:
+// the walk starts XdrMsg::pay_off bytes into message m and the header hash is
+// the network-order u32 at XdrMsg::hash_off; a message shorter than pay_off
+// fails like one the schema runs past.
+enum XdrOp : int {
+    // out[m] = x, status[m] = 1 when the schema runs past the message.
+    kXdrChecksum,
+    // mchecksum_gpu_verify_xdr_messages: x is compared with the header hash:
+    // status[m], and the launch's count in *mism.
+    kXdrVerify,
+    // mchecksum_gpu_seal_xdr_messages: x is stored big-endian in the hash
+    // slot; a failed message gets status 1 and is not written.
+    kXdrSeal,
+    // mchecksum_gpu_unpack_xdr_messages: verify, and the hashed stream -- the
+    // little-endian image of every INT, the bytes of every opaque or raw
+    // field -- is also stored at dst[dst_off[m], dst_off[m + 1]) by the walk
+    // that hashes it.  The decoded length depends on the data, so the INT
+    // fields are walked once for it first (xdr_decoded_len): a message whose
+    // decoded length is not its slot's gets status 1, one mismatch and no
+    // byte written.
+    kXdrUnpack,
+};
+
+// The message operations' arguments beside XdrArgs (whose `out` they leave unused).
+struct XdrMsg {
+    uint64_t pay_off, hash_off;
+    uint8_t *dst;             // unpack
+    const uint64_t *dst_off;  // unpack: count + 1 entries
+    uint32_t *mism;           // verify, unpack
+};
+struct XdrMsgArgs {
+    XdrArgs a;
+    XdrMsg x;
+};
+
+// The length of the hashed stream of the message at [pos, end): the main
+// walk's steps and bounds tests, reading the INT fields only.  false: the
+// schema runs past the message.
+__device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, uint64_t end, uint64_t *n) {
+    uint64_t last = 0, total = 0;
+    for (uint32_t f = 0; f < a.nf; f++) {
+        const uint32_t kind = a.kind[f], sz = a.size[f];
+        if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
+            if (last == 0) f += sz;
+            continue;
+        }
+        if (kind == MCHECKSUM_XDR_INT) {
+            const uint32_t slot = sz <= 4 ? 4u : 8u;
+            if (end - pos < slot) return false;
+            uint64_t v = 0;
+            for (uint32_t b = 0; b < slot; b++) v = v << 8 | a.buf[pos + b];
+            last = sz == 8 ? v : v & ((1ull << (8 * sz)) - 1);
+            total += sz;
+            pos += slot;
+            continue;
+        }
+        const bool raw = kind == MCHECKSUM_XDR_RAW || kind == MCHECKSUM_XDR_RAW_LEN;
+        const uint64_t len = (kind == MCHECKSUM_XDR_OPAQUE_LEN || kind == MCHECKSUM_XDR_RAW_LEN) ? last : sz;
+        if (len > end - pos || (!raw && ((len + 3) & ~3ull) > end - pos)) return false;
+        total += len;  // (every field lies inside the message: no overflow)
+        pos += raw ? len : (len + 3) & ~3ull;
+    }
+    *n = total;
+    return true;
+}
+
+// One message (one wave, wave-uniform walk): the checksum writes out[m] and
+// status[m]; the message operations (XdrOp) end in their own epilogues and
+// count failures in lane 0's nbad (add_mismatches).
+// fast(p, len, &L, d) may hash an opaque/raw field of len bytes at p itself,
+// continuing the running register L (returning true) and, unpack, storing the
+// bytes at d; otherwise 64 lane ranges are hashed -- and copied -- byte by
+// byte and combined into L.
+template <int W, int OP = kXdrChecksum, class Fast>
+__device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, uint64_t m, const xdr_reg_t<W> *tab,
+                                            uint32_t lane, Fast &&fast, uint32_t &nbad) {
     using R = xdr_reg_t<W>;
+    enum : bool { MSG = OP != kXdrChecksum, VERIFY = OP == kXdrVerify || OP == kXdrUnpack, COPY = OP == kXdrUnpack };
+    static_assert(!MSG || W == 32, "the header's hash slot is 32 bits");
     uint64_t pos = a.off[m];
     const uint64_t end = a.off[m + 1];
+    [[maybe_unused]] const uint64_t m0 = pos;
     R acc = (R)a.init;
     uint64_t last = 0;
     bool bad = end < pos;
+    if constexpr (MSG) {
+        bad = bad || end - pos < x.pay_off;
+        pos += x.pay_off;
+    }
+    // unpack: where the next decoded byte goes.  A message that does not fit
+    // its slot is not walked at all: nothing of it is hashed or stored.
+    [[maybe_unused]] uint8_t *d = nullptr;
+    if constexpr (COPY) {
+        const uint64_t d0 = x.dst_off[m], d1 = x.dst_off[m + 1];
+        uint64_t n = 0;
+        bad = bad || d1 < d0 || !xdr_decoded_len(a, pos, end, &n) || n != d1 - d0;
+        d = x.dst + d0;
+    }
     for (uint32_t f = 0; f < a.nf && !bad; f++) {
         const uint32_t kind = a.kind[f], sz = a.size[f];
         if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
@@ -1094,6 +1183,12 @@ __device__ __forceinline__ void xdr_message(const XdrArgs &a, uint64_t m, const 
             uint64_t v = 0;
             for (uint32_t b = 0; b < slot; b++) v = v << 8 | a.buf[pos + b];
             for (uint32_t b = 0; b < sz; b++) acc = (acc >> 8) ^ tab[(uint32_t)(acc ^ (R)(v >> (8 * b))) & 0xFFu];
+            if constexpr (COPY) {
+                // the host-order image, at any byte address: byte stores from lane 0
+                if (lane == 0)
+                    for (uint32_t b = 0; b < sz; b++) d[b] = (uint8_t)(v >> (8 * b));
+                d += sz;
+            }
             last = sz == 8 ? v : v & ((1ull << (8 * sz)) - 1);
             pos += slot;
             continue;
@@ -1104,21 +1199,37 @@ __device__ __forceinline__ void xdr_message(const XdrArgs &a, uint64_t m, const 
             bad = true;
             break;
         }
-        if (!fast(a.buf + pos, len, &acc)) {
+        if (!fast(a.buf + pos, len, &acc, d)) {
             R p = 0;
             const uint64_t chunk = (len + 63) / 64;
             const uint64_t lo = lane * chunk < len ? lane * chunk : len, hi = lo + chunk < len ? lo + chunk : len;
-            for (uint64_t i = lo; i < hi; i++) p = (p >> 8) ^ tab[(uint32_t)(p ^ a.buf[pos + i]) & 0xFFu];
+            for (uint64_t i = lo; i < hi; i++) {
+                const uint8_t byte = a.buf[pos + i];
+                if constexpr (COPY) d[i] = byte;  // the lane's own range of the field: no byte outside it
+                p = (p >> 8) ^ tab[(uint32_t)(p ^ byte) & 0xFFu];
+            }
             p = xdr_shift<W>(a.shift, p, len - hi);
 #pragma unroll
             for (int k = 1; k < 64; k <<= 1) p ^= __shfl_xor(p, k, 64);
             acc = xdr_shift<W>(a.shift, acc, len) ^ p;
         }
+        if constexpr (COPY) d += len;
         pos += raw ? len : (len + 3) & ~3ull;
     }
     if (lane == 0) {
         const R crc = bad ? (R)0 : acc ^ (R)a.xorout;
-        reinterpret_cast<R *>(a.out)[m] = crc;
+        if constexpr (!MSG) {
+            reinterpret_cast<R *>(a.out)[m] = crc;
+        } else if constexpr (OP == kXdrSeal) {
+            // In place: the slot lies in the message's headers, outside every
+            // hashed byte, so no value depends on whether another wave's
+            // 16-byte loads around a field see its old or its new bytes.
+            if (!bad) store_be32(const_cast<uint8_t *>(a.buf) + m0 + x.hash_off, (uint32_t)crc);
+        } else {
+            // (unpack: the bytes are stored as decoded; the value is known only after them)
+            bad = bad || load_be32(a.buf + m0 + x.hash_off) != (uint32_t)crc;
+            nbad += bad;
+        }
         if (a.status) a.status[m] = bad ? 1 : 0;
     }
 }
@@ -1132,8 +1243,27 @@ __global__ __launch_bounds__(256) void xdr_kernel(XdrArgs a) {
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nw = (uint64_t)gridDim.x * 4;
+    uint32_t nbad = 0;  // (the message operations' count: unused here)
     for (uint64_t m = uniform((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6))); m < a.count; m += nw)
-        xdr_message<W>(a, m, tab, lane, [](const uint8_t *, uint64_t, R *) { return false; });
+        xdr_message<W>(a, XdrMsg{}, m, tab, lane, [](const uint8_t *, uint64_t, R *, uint8_t *) { return false; }, nbad);
+}
+
+// The message operations in the latency layout (32-bit models): no wait on
+// the device, so nothing to fail closed on.
+template <int OP>
+__global__ __launch_bounds__(256) void xdr_msg_kernel(XdrMsgArgs ma) {
+    const XdrArgs &a = ma.a;
+    const XdrMsg &x = ma.x;
+    __shared__ uint32_t tab[256];
+    tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    uint32_t nbad = 0;
+    for (uint64_t m = uniform((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6))); m < a.count; m += nw)
+        xdr_message<32, OP>(a, x, m, tab, lane, [](const uint8_t *, uint64_t, uint32_t *, uint8_t *) { return false; },
+                            nbad);
+    if constexpr (OP != kXdrSeal) add_mismatches(x.mism, nbad);  // once per workgroup (crc_gpu_common.h)
 }
 
 // Throughput layout (large batches): persistent 1024-thread workgroups with the
@@ -1158,7 +1288,7 @@ __global__ __launch_bounds__(1024, 1) void xdr_fast_kernel(XdrArgs a) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 16u + (threadIdx.x >> 6));
     const uint32_t nw = gridDim.x * 16u;
     const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u, lc64 = (lane & 31u) << 3;
-    auto fast = [&](const uint8_t *p, uint64_t len, R *reg) -> bool {
+    auto fast = [&](const uint8_t *p, uint64_t len, R *reg, uint8_t *) -> bool {
         if (len < kXdrFastMin || len >= (1ull << 31)) return false;
         if constexpr (W == 32)
             *reg = payload32_g64<NT, Tab32<false>, true>(Tab32<false>{lds}, reinterpret_cast<const crc32_gpu_pack_t *>(a.pack),
@@ -1168,13 +1298,76 @@ __global__ __launch_bounds__(1024, 1) void xdr_fast_kernel(XdrArgs a) {
                                                        lane, lc64, *reg);
         return true;
     };
+    uint32_t nbad = 0;  // (the message operations' count: unused here)
     const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
-                                             [&](uint64_t m) { xdr_message<W>(a, m, tab, lane, fast); });
+                                             [&](uint64_t m) { xdr_message<W>(a, XdrMsg{}, m, tab, lane, fast, nbad); });
     if (faulted) {  // fail closed: the caller's error word, and every status flagged
         if (lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
         if (a.status)
             for (uint64_t m = lane; m < a.count; m += 64) a.status[m] = 1;
     }
+}
+
+// The message operations in the throughput layout: xdr_fast_kernel's
+// workgroups, tables and work queue for the 32-bit models; unpack hashes a
+// field of >= kXdrFastMin bytes with the step loop's copying twin, which
+// stores it at its place in the destination -- whole 16-byte pieces
+// unaligned, edge pieces byte by byte (crc_gpu_pack_store.h).
+// Fail closed: a launch whose wait gave up adds 1 to the error word and, where
+// there is a counter, `count` to it; its statuses are flagged after the
+// launch, once no wave can overwrite them (xdr_flag_kernel).
+// (The copying step loop is instantiated for a table type of this kernel's
+// own: the segment copy kernels' instance of it -- its inlined fold -- then
+// compiles as it did before this kernel called the same template.)
+struct XdrTab32 : Tab32<false> {};
+template <int OP, bool NT>
+__global__ __launch_bounds__(1024, 1) void xdr_msg_fast_kernel(XdrMsgArgs ma) {
+    const XdrArgs &a = ma.a;
+    const XdrMsg &x = ma.x;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kXdrMainLds<32> + 256 * sizeof(uint32_t)];
+    __shared__ WgQueue wgq;
+    uint32_t *tab = reinterpret_cast<uint32_t *>(lds + kXdrMainLds<32>);
+    if (threadIdx.x == 0) wg_queue_init(&wgq, a.queue, a.count);
+    const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
+    fill_lds32<false, 1024>(lds, pk);
+    if (threadIdx.x < 256) tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 16u + (threadIdx.x >> 6));
+    const uint32_t nw = gridDim.x * 16u;
+    const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
+    auto fast = [&](const uint8_t *p, uint64_t len, uint32_t *reg, [[maybe_unused]] uint8_t *d) -> bool {
+        if (len < kXdrFastMin || len >= (1ull << 31)) return false;
+        if constexpr (OP == kXdrUnpack)
+            *reg = payload32_g64<NT, XdrTab32, true, true>(XdrTab32{{lds}}, pk, p, len, lane, lc0, lc1, *reg, d);
+        else
+            *reg = payload32_g64<NT, Tab32<false>, true>(Tab32<false>{lds}, pk, p, len, lane, lc0, lc1, *reg);
+        return true;
+    };
+    uint32_t nbad = 0;
+    const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
+                                             [&](uint64_t m) { xdr_message<32, OP>(a, x, m, tab, lane, fast, nbad); });
+    if (faulted && lane == 0) {
+        if (a.err_word) atomicAdd(a.err_word, 1u);
+        if (OP != kXdrSeal && x.mism) atomicAdd(x.mism, (uint32_t)a.count);
+    }
+    if constexpr (OP != kXdrSeal) add_mismatches(x.mism, nbad);  // once per workgroup (crc_gpu_common.h)
+}
+
+// After a message operation's throughput launch that held a work-queue slot
+// (this launch holds the slot in its place, so the bank is still the call's):
+// if a wait of that launch gave up -- its fault flag is claimed -- every
+// status becomes 1.  The launch's own waves write verdicts until its end, so
+// only a launch after it can leave all of them flagged.
+struct XdrFlagArgs {
+    const unsigned long long *queue;
+    uint8_t *status;
+    uint64_t count;
+};
+__global__ __launch_bounds__(256) void xdr_flag_kernel(XdrFlagArgs f) {
+    if (!__hip_atomic_load(f.queue + kQFault * kQStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    for (uint64_t m = (uint64_t)blockIdx.x * 256 + threadIdx.x; m < f.count; m += (uint64_t)gridDim.x * 256)
+        f.status[m] = 1;
 }
 
 }  // namespace
@@ -1538,22 +1731,44 @@ int mchecksum_gpu_seal_core_headers(const char *hash_method, int kind, void *dev
     return core_headers_call(hash_method, kind, dev_buf, dev_msg_offsets, count, dev_status, nullptr, stream, true);
 }
 
-int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
-                               const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, void *dev_out,
-                               uint8_t *dev_status, void *stream) {
-    if ((nfields && !fields) || !dev_msg_offsets || (count && (!dev_buf || !dev_out)))
-        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+// The XDR entry points' schema check; the fields go into the kernel arguments.
+static int xdr_schema(const mchecksum_xdr_field_t *fields, size_t nfields, XdrArgs *a) {
     if (nfields > kXdrMaxFields) return set_err(MCHECKSUM_GPU_EINVAL, "more than %u schema fields", kXdrMaxFields);
-    XdrArgs a{};
     for (size_t f = 0; f < nfields; f++) {
         const uint32_t k = fields[f].kind, z = fields[f].size;
         const bool ok = (k == MCHECKSUM_XDR_INT && (z == 1 || z == 2 || z == 4 || z == 8)) ||
                         k == MCHECKSUM_XDR_OPAQUE || k == MCHECKSUM_XDR_RAW || k == MCHECKSUM_XDR_OPAQUE_LEN ||
                         k == MCHECKSUM_XDR_RAW_LEN || (k == MCHECKSUM_XDR_SKIP_IF_ZERO && z <= nfields - f - 1);
         if (!ok) return set_err(MCHECKSUM_GPU_EINVAL, "schema field %zu: bad kind %u / size %u", f, k, z);
-        a.kind[f] = k;
-        a.size[f] = z;
+        a->kind[f] = k;
+        a->size[f] = z;
     }
+    a->nf = (uint32_t)nfields;
+    return MCHECKSUM_GPU_OK;
+}
+
+// The model's words of the walk (register form).
+static void xdr_model(int idx, const void *shift, XdrArgs *a) {
+    const mck_model_t &m = mck_models[idx];
+    a->shift = shift;
+    a->rpoly = mck_reflect(m.poly, m.width);
+    a->init = mck_reflect(m.init, m.width);
+    a->xorout = m.xorout;
+}
+
+// throughput layout for batches past a receive queue's worth of RPCs
+// (MCHECKSUM_GPU_XDR_FAST=0/1 overrides)
+static bool xdr_fast_layout(const mck_settings_t &s, size_t count) {
+    return s.gpu_xdr_fast >= 0 ? s.gpu_xdr_fast == 1 : count > kRecvQueueBatch;
+}
+
+int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
+                               const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, void *dev_out,
+                               uint8_t *dev_status, void *stream) {
+    if ((nfields && !fields) || !dev_msg_offsets || (count && (!dev_buf || !dev_out)))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    XdrArgs a{};
+    if (int rc = xdr_schema(fields, nfields, &a)) return rc;
     Model model;
     const int found = gpu_model(hash_method, &model);
     if (found == -1) return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", hash_method ? hash_method : "(null)");
@@ -1566,26 +1781,19 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
     if (int rc = device_ctx(&c)) return rc;
     if (int rc = get_ext(c, idx, &shift)) return rc;
     if (count == 0) return MCHECKSUM_GPU_OK;
-    // throughput layout for batches past a receive queue's worth of RPCs
-    // (MCHECKSUM_GPU_XDR_FAST=0/1 overrides)
     const mck_settings_t &s = *mck_settings();
-    const bool fast = s.gpu_xdr_fast >= 0 ? s.gpu_xdr_fast == 1 : count > kRecvQueueBatch;
+    const bool fast = xdr_fast_layout(s, count);
     if (fast) {
         const void *pack = nullptr;
         if (int rc = get_pack(c, idx, CRC_GPU_MAX_LOG2G, &pack)) return rc;
         a.pack = pack;
     }
-    const mck_model_t &m = mck_models[idx];
     a.buf = (const uint8_t *)dev_buf;
     a.off = dev_msg_offsets;
     a.count = count;
     a.out = dev_out;
     a.status = dev_status;
-    a.shift = shift;
-    a.rpoly = mck_reflect(m.poly, m.width);
-    a.init = mck_reflect(m.init, m.width);
-    a.xorout = m.xorout;
-    a.nf = (uint32_t)nfields;
+    xdr_model(idx, shift, &a);
     if (fast) {
         // non-temporal loads for batches far past the Infinity Cache, sized
         // by count as for offsets batches (MCHECKSUM_GPU_NT=0/1 overrides)
@@ -1605,6 +1813,132 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
                                        (hipStream_t)stream, nullptr, a);
     if (e != hipSuccess) return hip_err(e, "XDR kernel launch");
     return MCHECKSUM_GPU_OK;
+}
+
+// The kernels of one message operation: the latency layout's, and the
+// throughput layout's with default and non-temporal loads.
+struct XdrMsgKernels {
+    void (*lat)(XdrMsgArgs);
+    void (*fast)(XdrMsgArgs);
+    void (*fast_nt)(XdrMsgArgs);
+};
+#define MCK_XDR_MSG_KERNELS(OP) \
+    XdrMsgKernels { xdr_msg_kernel<OP>, xdr_msg_fast_kernel<OP, false>, xdr_msg_fast_kernel<OP, true> }
+
+// One message call (verify_xdr_messages, seal_xdr_messages,
+// unpack_xdr_messages): the argument checks in the header's order, then
+// checksum_xdr's choice of layout, slot and loads.
+struct XdrMsgCall {
+    XdrOp op;
+    const char *method;
+    const mchecksum_xdr_field_t *fields;
+    size_t nfields;
+    const void *buf;
+    const uint64_t *off;
+    size_t count, pay_off, hash_off;
+    uint8_t *status;
+    void *stream;
+    void *dst = nullptr;
+    const uint64_t *dst_off = nullptr;
+    uint32_t *mism = nullptr;
+};
+
+static int xdr_msg_call(const XdrMsgCall &mc) {
+    const size_t count = mc.count;
+    const bool unpack = mc.op == kXdrUnpack;
+    if ((mc.nfields && !mc.fields) || (count && (!mc.buf || !mc.off || (unpack && (!mc.dst || !mc.dst_off)))))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (mc.hash_off > mc.pay_off || mc.pay_off - mc.hash_off < 4)
+        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
+    if ((uint64_t)count > (1ull << 31)) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 messages in one call");
+    XdrMsgArgs ma{};
+    XdrArgs &a = ma.a;
+    if (int rc = xdr_schema(mc.fields, mc.nfields, &a)) return rc;
+    Model model;
+    const int found = gpu_model(mc.method, &model);
+    if (found == -1)
+        return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", mc.method ? mc.method : "(null)");
+    if (found < 0 || model.msb || model.width != 32)
+        return set_err(MCHECKSUM_GPU_EMETHOD,
+                       "the message header carries a 32-bit hash: \"%s\" is not a reflected 32-bit method", mc.method);
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    DevCtx *c = nullptr;
+    const void *shift = nullptr;
+    if (int rc = device_ctx(&c)) return rc;
+    if (int rc = get_ext(c, model.idx, &shift)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    const mck_settings_t &s = *mck_settings();
+    const bool fast = xdr_fast_layout(s, count);
+    if (fast) {
+        const void *pack = nullptr;
+        if (int rc = get_pack(c, model.idx, CRC_GPU_MAX_LOG2G, &pack)) return rc;
+        a.pack = pack;
+    }
+    a.buf = (const uint8_t *)mc.buf;
+    a.off = mc.off;
+    a.count = count;
+    a.status = mc.status;
+    xdr_model(model.idx, shift, &a);
+    ma.x = XdrMsg{mc.pay_off, mc.hash_off, (uint8_t *)mc.dst, mc.dst_off, mc.mism};
+    const XdrMsgKernels ks = mc.op == kXdrVerify ? MCK_XDR_MSG_KERNELS(kXdrVerify)
+                             : mc.op == kXdrSeal ? MCK_XDR_MSG_KERNELS(kXdrSeal)
+                                                 : MCK_XDR_MSG_KERNELS(kXdrUnpack);
+    if (!fast) {
+        uint64_t blocks = (count + 3) / 4;
+        if (blocks > (uint64_t)c->cus * 8) blocks = (uint64_t)c->cus * 8;
+        const hipError_t e = launch_kernel(ks.lat, dim3((unsigned)blocks), dim3(256), (hipStream_t)mc.stream, nullptr, ma);
+        return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "XDR message kernel launch");
+    }
+    a.err_word = error_word();
+    uint64_t blocks = (count + 15) / 16;
+    if (blocks > (uint64_t)c->cus) blocks = (uint64_t)c->cus;
+    SlotRef sr = queue_slot(c, mc.stream);
+    a.queue = sr.q;
+    const auto k = nt_by_count(s, count) ? ks.fast_nt : ks.fast;
+    // Without a slot (a captured call: static split, no wait on the device)
+    // or without statuses there is nothing to flag after the launch.
+    if (!sr.q || !mc.status) return launch_slot(c, sr, k, (unsigned)blocks, 1024, mc.stream, ma, "XDR message kernel launch");
+    // Fail closed: the flagging launch takes over the slot -- its completion
+    // frees it -- so the bank it reads is still this call's.
+    const hipError_t e = launch_kernel(k, dim3((unsigned)blocks), dim3(1024), (hipStream_t)mc.stream, nullptr, ma);
+    if (e != hipSuccess) {
+        slot_unissue(c, sr);
+        return hip_err(e, "XDR message kernel launch");
+    }
+    uint64_t fb = (count + 4095) / 4096;
+    if (fb > (uint64_t)c->cus * 4) fb = (uint64_t)c->cus * 4;
+    return launch_slot(c, sr, xdr_flag_kernel, (unsigned)fb, 256, mc.stream, XdrFlagArgs{sr.q, mc.status, count},
+                       "XDR status launch");
+}
+
+int mchecksum_gpu_verify_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
+                                      const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+                                      size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+                                      uint32_t *dev_mismatches, void *stream) {
+    XdrMsgCall mc{kXdrVerify, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
+                  dev_status, stream};
+    mc.mism = dev_mismatches;
+    return xdr_msg_call(mc);
+}
+
+int mchecksum_gpu_seal_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
+                                    void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                    size_t hash_offset, uint8_t *dev_status, void *stream) {
+    return xdr_msg_call({kXdrSeal, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
+                         hash_offset, dev_status, stream});
+}
+
+int mchecksum_gpu_unpack_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
+                                      const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+                                      size_t payload_offset, size_t hash_offset, void *dev_dst,
+                                      const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_mismatches,
+                                      void *stream) {
+    XdrMsgCall mc{kXdrUnpack, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
+                  dev_status, stream};
+    mc.dst = dev_dst;
+    mc.dst_off = dev_dst_offsets;
+    mc.mism = dev_mismatches;
+    return xdr_msg_call(mc);
 }
 
 }  // extern "C"

@@ -1033,6 +1033,100 @@ def checksum_xdr(method: str, data: torch.Tensor, msg_offsets: torch.Tensor, sch
     return (out, st) if status else out
 
 
+def _xdr_fields(schema):
+    from ._lib import XdrField
+    return (XdrField * max(1, len(schema)))(*[XdrField(int(k), int(z)) for k, z in schema])
+
+
+def verify_xdr_messages(method: str, data: torch.Tensor, msg_offsets: torch.Tensor, schema, payload_offset: int = 20,
+                        hash_offset: int = 16, stream=None, offsets_host=None, status=None, mismatches=None):
+    """verify_messages for a Mercury built with XDR encoding
+    (mchecksum_gpu_verify_xdr_messages): each message's proc buffer starts at
+    payload_offset and is walked with checksum_xdr's schema; the value is
+    compared with the network-order u32 at hash_offset.  Returns (status uint8
+    per message: 1 = short, truncated or a different CRC; count).  status and
+    mismatches: None allocates, False passes NULL, a tensor is reused (the
+    call adds to a counter the caller zeroed)."""
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    status, mism = _verdict_buffers(count, data.device, status, mismatches)
+    _same_device(data, msg_offsets=msg_offsets)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_verify_xdr_messages(method.encode(), _xdr_fields(schema), len(schema),
+                                                      data.data_ptr(), msg_offsets.data_ptr(), count, payload_offset,
+                                                      hash_offset, _ptr(status), _ptr(mism),
+                                                      _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_xdr_messages")
+    return status, mism
+
+
+def seal_xdr_messages(method: str, data: torch.Tensor, msg_offsets: torch.Tensor, schema, payload_offset: int = 20,
+                      hash_offset: int = 16, stream=None, offsets_host=None, status=None) -> torch.Tensor:
+    """Sender side of verify_xdr_messages, in place
+    (mchecksum_gpu_seal_xdr_messages): the proc checksum of each message is
+    stored network-order at hash_offset.  Returns status (uint8 per message: 1
+    = short or truncated, not written).  Only the 4 hash bytes of each sealed
+    message are written.  Pass a preallocated `status` (uint8, >= count,
+    filled with ones) to reuse it."""
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    status = _sender_status(data, count, status)
+    _same_device(data, msg_offsets=msg_offsets, status=status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_seal_xdr_messages(method.encode(), _xdr_fields(schema), len(schema),
+                                                    data.data_ptr(), msg_offsets.data_ptr(), count, payload_offset,
+                                                    hash_offset, status.data_ptr(),
+                                                    _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_xdr_messages")
+    return status
+
+
+def unpack_xdr_messages(method: str, data: torch.Tensor, msg_offsets: torch.Tensor, schema, dst: torch.Tensor,
+                        dst_offsets: torch.Tensor, payload_offset: int = 20, hash_offset: int = 16, stream=None,
+                        offsets_host=None, dst_offsets_host=None, status=None, mismatches=None):
+    """verify_xdr_messages that also decodes, in one pass
+    (mchecksum_gpu_unpack_xdr_messages): the hashed stream of message i -- its
+    non-XDR image: every integer's host-order bytes, every byte array without
+    its pad -- goes to dst[dst_offsets[i] : dst_offsets[i+1]].  Returns
+    (status, count) with verify_xdr_messages' buffer rules.  Status 1 = the
+    CRC differs (the destination then holds the bytes as decoded) or the
+    message is short, truncated or its decoded length is not its slot's
+    (nothing of it is written).  The decoded lengths depend on the data, so
+    only the tables' bounds are checked here; with both host tables given the
+    two ranges must not overlap."""
+    _check_device_u8(data, "data")
+    _check_device_u8(dst, "dst")
+    _check_offsets(data, msg_offsets, offsets_host)
+    _check_offsets(dst, dst_offsets, dst_offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0 or dst_offsets.numel() != count + 1:
+        raise GpuChecksumError("msg_offsets and dst_offsets need the same number (>= 1) of entries")
+    if offsets_host is not None and dst_offsets_host is not None and count:
+        import numpy as np
+        mo, do = np.asarray(offsets_host, dtype=np.uint64), np.asarray(dst_offsets_host, dtype=np.uint64)
+        s0, d0 = data.data_ptr() + int(mo[0]), dst.data_ptr() + int(do[0])
+        if s0 < d0 + int(do[-1] - do[0]) and d0 < s0 + int(mo[-1] - mo[0]):
+            raise GpuChecksumError("the message and destination ranges overlap")
+    status, mism = _verdict_buffers(count, data.device, status, mismatches)
+    _same_device(data, msg_offsets=msg_offsets, dst=dst, dst_offsets=dst_offsets)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_unpack_xdr_messages(method.encode(), _xdr_fields(schema), len(schema),
+                                                      data.data_ptr(), msg_offsets.data_ptr(), count, payload_offset,
+                                                      hash_offset, dst.data_ptr(), dst_offsets.data_ptr(),
+                                                      _ptr(status), _ptr(mism), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_xdr_messages")
+    return status, mism
+
+
 def fill_splitmix(t: torch.Tensor, seed: int, first_word: int = 0, stream=None) -> torch.Tensor:
     """Fill a device tensor with the synthetic payload bytes of SURVEY.md 8(d)."""
     _check_device_u8(t, "tensor")
