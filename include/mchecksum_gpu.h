@@ -61,6 +61,14 @@
  * calls do (status 1 on every message the launch cannot vouch for; the hash
  * slots of such messages are unspecified) and are capture-safe after
  * mchecksum_gpu_prepare(): a replay packs or seals the current contents again.
+ * For a Mercury built with XDR encoding, mchecksum_gpu_pack_xdr_messages is
+ * the same one pass with an encoder in it: it reads each message's host-order
+ * field values, writes their XDR wire bytes behind the headers, hashes the
+ * values and seals (what hg_proc_<type> does per field on HG_ENCODE under
+ * HG_HAS_XDR: xdr_<type> into the buffer, mchecksum_update over the host
+ * variable, src/mercury_proc.h:110-122,147-160);
+ * mchecksum_gpu_seal_xdr_messages hashes messages already encoded, and
+ * mchecksum_gpu_xdr_encoded_sizes gives the message table's lengths.
  *
  * Receiver side: mchecksum_gpu_verify_messages checks received messages in
  * place; mchecksum_gpu_unpack_messages also copies each payload out of the
@@ -650,6 +658,15 @@ mchecksum_gpu_seal_core_headers(const char *hash_method, int kind,
  *   MCHECKSUM_XDR_SKIP_IF_ZERO if the last INT field was 0, skip the next
  *                             `size` schema entries (an empty hg_string_t
  *                             carries no bytes and no flags)
+ *   MCHECKSUM_XDR_SINT        INT for a signed type (hg_proc_int<8*size>_t):
+ *                             mchecksum_gpu_pack_xdr_messages sign-extends a
+ *                             1-, 2- or 4-byte value into its 32-bit word
+ *                             where INT zero-extends.  Every other call
+ *                             treats it exactly as INT -- the low `size`
+ *                             bytes are hashed and decoded, and the value a
+ *                             following _LEN or SKIP entry reads is the
+ *                             zero-extended one -- so one schema serves
+ *                             sender and receiver
  * Message i = dev_buf[dev_msg_offsets[i], dev_msg_offsets[i+1]) starting
  * where the proc buffer starts; dev_out[i] = the value hg_proc_checksum_get
  * returns for it (host-order, method size).  dev_status[i] (optional) = 1
@@ -661,6 +678,7 @@ mchecksum_gpu_seal_core_headers(const char *hash_method, int kind,
 #define MCHECKSUM_XDR_RAW          3
 #define MCHECKSUM_XDR_RAW_LEN      4
 #define MCHECKSUM_XDR_SKIP_IF_ZERO 5
+#define MCHECKSUM_XDR_SINT         6
 typedef struct mchecksum_xdr_field {
     uint32_t kind;
     uint32_t size;
@@ -733,6 +751,85 @@ mchecksum_gpu_unpack_xdr_messages(const char *hash_method,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
     uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
+
+/* XDR-mode sender: encode, hash and seal in one pass -- what
+ * mchecksum_gpu_pack_messages is for the default build, and the mirror of
+ * mchecksum_gpu_unpack_xdr_messages.  Source i = dev_src[dev_src_offsets[i],
+ * dev_src_offsets[i+1]) (count + 1 entries, as dev_msg_offsets) is message
+ * i's non-XDR image in schema order: the little-endian `size` bytes of every
+ * INT / SINT, then the unpadded bytes of every OPAQUE and RAW field -- byte
+ * for byte what unpack_xdr_messages writes.  It may start at any byte and
+ * must be readable up to the next 16-byte boundary.  The walk follows the
+ * schema over the image and writes its XDR encoding to
+ * dev_buf[dev_msg_offsets[i] + payload_offset, dev_msg_offsets[i+1]):
+ * integers big-endian in 4- or 8-byte slots (INT zero-extended, SINT
+ * sign-extended), OPAQUE bytes followed by a zero pad to a multiple of 4, RAW
+ * fields at their exact size; a _LEN field takes its byte count from the
+ * preceding integer as read from the image, SKIP_IF_ZERO as in the other
+ * calls.  In the same read it hashes the image -- the hashed stream -- and
+ * stores the value big-endian in the 4 bytes at dev_msg_offsets[i] +
+ * hash_offset.
+ *
+ * Message i fits iff the schema consumes the image exactly (it neither runs
+ * past the image's end nor stops short of it) and dev_msg_offsets[i+1] -
+ * dev_msg_offsets[i] == payload_offset + the encoded length, with no slack
+ * (mchecksum_gpu_xdr_encoded_sizes computes that length).  A message that
+ * does not fit gets dev_status[i] = 1 and no byte of it is written; a packed
+ * one gets 0 (dev_status may be NULL).  Exactly the XDR bytes (pads included)
+ * and the 4 hash bytes of fitting messages are written: no other header byte,
+ * nothing before, between or after them, and dev_src is never written.  The
+ * source and destination ranges must not overlap (not checked).
+ *
+ * Methods, the order of the argument checks (the NULL pointers here: fields,
+ * dev_src, dev_src_offsets, dev_buf, dev_msg_offsets), layout, work-queue slot
+ * and graph capture as the other XDR message calls (capture-safe after
+ * mchecksum_gpu_prepare(); a replay reads the current contents and tables).
+ * Fail closed, like seal: a call whose throughput layout gave up a wait adds
+ * 1 to the error word and sets every status to 1; the written bytes of
+ * messages it cannot vouch for are unspecified.  There is no mismatch counter
+ * on the sender side.
+ *
+ * Cost (MI355X): the one pass takes 0.77x (8192 x 64 KiB) and
+ * 0.87x (65536 x 4 KiB) the time of a device copy of the wire bytes followed
+ * by mchecksum_gpu_seal_xdr_messages, and what unpack_xdr_messages takes. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_xdr_messages(const char *hash_method,
+    const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_src,
+    const uint64_t *dev_src_offsets, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
+/* The data-dependent lengths the XDR message tables are built from, computed
+ * where the data is: one small launch per call that reads the integer fields
+ * only, with the walks' own bounds tests.
+ *
+ * encoded_sizes: dev_sizes[i] = the XDR length pack_xdr_messages would write
+ *   for image i = dev_src[dev_src_offsets[i], dev_src_offsets[i+1]); 0, with
+ *   dev_status[i] = 1, when the schema does not consume the image exactly.
+ *   An exclusive prefix sum of payload_offset + dev_sizes is the message
+ *   table pack_xdr_messages accepts.
+ * decoded_sizes: dev_sizes[i] = the decoded length of message i (what decides
+ *   unpack_xdr_messages' fit; their exclusive prefix sum is its destination
+ *   table); dev_wire_sizes[i] (optional, may be NULL) = the XDR bytes the
+ *   schema consumed from payload_offset on, so a receiver can tell the slack.
+ *   Both are 0, with dev_status[i] = 1, when the message is shorter than
+ *   payload_offset or the schema runs past it.
+ *
+ * dev_status may be NULL; a sized entry gets 0.  No hash method, no tables,
+ * no work-queue slot, no workspace and no wait on the device: nothing to fail
+ * closed on, and capture-safe without mchecksum_gpu_prepare().
+ * MCHECKSUM_GPU_EINVAL (NULL pointers, a bad schema, count > 2^31) comes
+ * before the device check; count == 0 needs no buffers. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_xdr_encoded_sizes(const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_src, const uint64_t *dev_src_offsets,
+    size_t count, uint64_t *dev_sizes, uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_xdr_decoded_sizes(const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_buf, const uint64_t *dev_msg_offsets,
+    size_t count, size_t payload_offset, uint64_t *dev_sizes,
+    uint64_t *dev_wire_sizes, uint8_t *dev_status, void *stream);
 
 /* Lanes cooperating on one payload that checksum_fixed would choose for
  * this length (1..64) in a batch large enough to fill the device; a smaller

@@ -32,10 +32,11 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_update_segments", "mchecksum_gpu_update_gather_segments",
                "mchecksum_gpu_update_scatter_segments", "mchecksum_gpu_verify_segments", "mchecksum_gpu_state_verify",
                "mchecksum_gpu_verify_xdr_messages", "mchecksum_gpu_seal_xdr_messages",
-               "mchecksum_gpu_unpack_xdr_messages")
+               "mchecksum_gpu_unpack_xdr_messages", "mchecksum_gpu_pack_xdr_messages",
+               "mchecksum_gpu_xdr_encoded_sizes", "mchecksum_gpu_xdr_decoded_sizes")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
-XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
+XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
 
 
 class XdrField(ctypes.Structure):
@@ -128,6 +129,18 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_seal_xdr_messages.restype = c_int
     L.mchecksum_gpu_unpack_xdr_messages.argtypes = xdr_msg + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mchecksum_gpu_unpack_xdr_messages.restype = c_int
+    # (method, fields, nfields, src, src_offsets, buf, msg_offsets, count, payload_offset, hash_offset, status, stream)
+    L.mchecksum_gpu_pack_xdr_messages.argtypes = [c_char_p, ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p]
+    L.mchecksum_gpu_pack_xdr_messages.restype = c_int
+    # (fields, nfields, src, src_offsets, count, sizes, status, stream)
+    L.mchecksum_gpu_xdr_encoded_sizes.argtypes = [ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_xdr_encoded_sizes.restype = c_int
+    # (fields, nfields, buf, msg_offsets, count, payload_offset, sizes, wire_sizes, status, stream)
+    L.mchecksum_gpu_xdr_decoded_sizes.argtypes = [ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p, c_size_t,
+                                                  c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_xdr_decoded_sizes.restype = c_int
     L.mchecksum_gpu_state_init.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p]
     L.mchecksum_gpu_state_init.restype = c_int
     L.mchecksum_gpu_update_offsets.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]

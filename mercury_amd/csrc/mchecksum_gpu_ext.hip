@@ -1091,6 +1091,11 @@ enum XdrOp : int {
     // decoded length is not its slot's gets status 1, one mismatch and no
     // byte written.
     kXdrUnpack,
+    // mchecksum_gpu_pack_xdr_messages: the sender's mirror of unpack -- the
+    // walk reads the non-XDR image, stores its XDR encoding into the message
+    // and seals it (xdr_pack_message, a sibling walker with arguments and
+    // kernels of its own: XdrPackArgs).
+    kXdrPack,
 };
 
 // The message operations' arguments beside XdrArgs (whose `out` they leave unused).
@@ -1108,8 +1113,10 @@ struct XdrMsgArgs {
 // The length of the hashed stream of the message at [pos, end): the main
 // walk's steps and bounds tests, reading the INT fields only.  false: the
 // schema runs past the message.
-__device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, uint64_t end, uint64_t *n) {
+__device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, uint64_t end, uint64_t *n,
+                                                uint64_t *wire = nullptr) {
     uint64_t last = 0, total = 0;
+    const uint64_t pos0 = pos;
     for (uint32_t f = 0; f < a.nf; f++) {
         const uint32_t kind = a.kind[f], sz = a.size[f];
         if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
@@ -1133,6 +1140,7 @@ __device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, 
         pos += raw ? len : (len + 3) & ~3ull;
     }
     *n = total;
+    if (wire) *wire = pos - pos0;  // (the size calls: the XDR bytes the schema consumed)
     return true;
 }
 
@@ -1368,6 +1376,210 @@ __global__ __launch_bounds__(256) void xdr_flag_kernel(XdrFlagArgs f) {
     if (!__hip_atomic_load(f.queue + kQFault * kQStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
     for (uint64_t m = (uint64_t)blockIdx.x * 256 + threadIdx.x; m < f.count; m += (uint64_t)gridDim.x * 256)
         f.status[m] = 1;
+}
+
+// -------------------------------------------------------- XDR encoder ----
+//
+// mchecksum_gpu_pack_xdr_messages (kXdrPack): unpack's walk with the two
+// counters' roles swapped.  The wave reads message m's non-XDR image --
+// what unpack writes: every integer's little-endian `size` bytes, every
+// opaque or raw field's unpadded bytes -- from src[src_off[m], src_off[m+1]),
+// advancing by image strides; it hashes those bytes (they are the hashed
+// stream) and stores their XDR encoding from pay_off bytes into message m of
+// a.buf on, advancing by XDR strides.  The stores are unpack's: an integer's
+// big-endian slot by byte stores from lane 0, a field on the lane-range path
+// byte by byte by the lane that hashes it, a field of >= kXdrFastMin bytes in
+// the throughput layout by the copying step loop; one lane writes the zero
+// pad behind an opaque field.  The encoded length depends on the data, so the
+// image's integers are walked once first (xdr_encoded_len): a message whose
+// image the schema does not consume exactly, or whose slot is not pay_off +
+// the encoded length, is not walked at all -- status 1, no byte written.
+// A sibling of xdr_message, not a fifth variant of it: the existing kernels
+// keep their source.
+struct XdrPack {
+    const uint8_t *src;       // the images
+    const uint64_t *src_off;  // count + 1 entries
+    uint64_t sint;            // bit f: schema entry f is an INT of a signed type (MCHECKSUM_XDR_SINT)
+};
+struct XdrPackArgs {
+    XdrArgs a;
+    XdrMsg x;
+    XdrPack p;
+};
+
+// The little-endian image of an INT of sz bytes at p.
+__device__ __forceinline__ uint64_t xdr_image_int(const uint8_t *p, uint32_t sz) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < sz; b++) v |= (uint64_t)p[b] << (8 * b);
+    return v;
+}
+
+// The XDR length of the image img[0, end): xdr_decoded_len's twin, reading
+// the image's INT fields only.  false: the schema runs past the image or
+// stops short of its end.
+__device__ __forceinline__ bool xdr_encoded_len(const XdrArgs &a, const uint8_t *img, uint64_t end, uint64_t *n) {
+    uint64_t last = 0, total = 0, pos = 0;
+    for (uint32_t f = 0; f < a.nf; f++) {
+        const uint32_t kind = a.kind[f], sz = a.size[f];
+        if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
+            if (last == 0) f += sz;
+            continue;
+        }
+        if (kind == MCHECKSUM_XDR_INT) {
+            if (end - pos < sz) return false;
+            last = xdr_image_int(img + pos, sz);
+            total += sz <= 4 ? 4u : 8u;
+            pos += sz;
+            continue;
+        }
+        const bool raw = kind == MCHECKSUM_XDR_RAW || kind == MCHECKSUM_XDR_RAW_LEN;
+        const uint64_t len = (kind == MCHECKSUM_XDR_OPAQUE_LEN || kind == MCHECKSUM_XDR_RAW_LEN) ? last : sz;
+        if (len > end - pos) return false;
+        total += raw ? len : (len + 3) & ~3ull;  // (len <= the image's length: no overflow)
+        pos += len;
+    }
+    *n = total;
+    return pos == end;
+}
+
+// One message (one wave, wave-uniform walk).  fast(s, len, &L, d) as in
+// xdr_message: it may hash the field of len bytes at s itself, continuing L,
+// and store it at d.
+template <class Fast>
+__device__ __forceinline__ void xdr_pack_message(const XdrArgs &a, const XdrMsg &x, const XdrPack &p, uint64_t m,
+                                                 const uint32_t *tab, uint32_t lane, Fast &&fast) {
+    const uint64_t m0 = a.off[m], end = a.off[m + 1];
+    const uint64_t s0 = p.src_off[m], s1 = p.src_off[m + 1];
+    bool bad = end < m0 || s1 < s0 || end - m0 < x.pay_off;
+    uint64_t n = 0;
+    bad = bad || !xdr_encoded_len(a, p.src + s0, s1 - s0, &n) || n != end - m0 - x.pay_off;
+    const uint8_t *s = p.src + s0;                                // the next image byte
+    const uint8_t *const s_end = p.src + s1;
+    uint8_t *d = const_cast<uint8_t *>(a.buf) + m0 + x.pay_off;  // where the next XDR byte goes
+    uint8_t *const d_end = const_cast<uint8_t *>(a.buf) + end;
+    uint32_t acc = (uint32_t)a.init;
+    uint64_t last = 0;
+    for (uint32_t f = 0; f < a.nf && !bad; f++) {
+        const uint32_t kind = a.kind[f], sz = a.size[f];
+        if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
+            if (last == 0) f += sz;
+            continue;
+        }
+        // (the bounds tests again, on both sides: an image changed under the call moves no store out of the slot)
+        if (kind == MCHECKSUM_XDR_INT) {
+            const uint32_t slot = sz <= 4 ? 4u : 8u;
+            if ((uint64_t)(s_end - s) < sz || (uint64_t)(d_end - d) < slot) {
+                bad = true;
+                break;
+            }
+            const uint64_t v = xdr_image_int(s, sz);
+            for (uint32_t b = 0; b < sz; b++) acc = (acc >> 8) ^ tab[(acc ^ (uint32_t)(v >> (8 * b))) & 0xFFu];
+            // xdr_<type>: a signed type's value is sign-extended into its 32-bit word, an unsigned one's zero-extended
+            uint64_t w = v;
+            if (sz < 8 && ((p.sint >> f) & 1u) && ((v >> (8 * sz - 1)) & 1u)) w |= ~0ull << (8 * sz);
+            if (lane == 0)
+                for (uint32_t b = 0; b < slot; b++) d[b] = (uint8_t)(w >> (8 * (slot - 1 - b)));
+            last = v;
+            s += sz;
+            d += slot;
+            continue;
+        }
+        const bool raw = kind == MCHECKSUM_XDR_RAW || kind == MCHECKSUM_XDR_RAW_LEN;
+        const uint64_t len = (kind == MCHECKSUM_XDR_OPAQUE_LEN || kind == MCHECKSUM_XDR_RAW_LEN) ? last : sz;
+        const uint64_t wire = raw ? len : (len + 3) & ~3ull;
+        if (len > (uint64_t)(s_end - s) || wire < len || wire > (uint64_t)(d_end - d)) {
+            bad = true;
+            break;
+        }
+        if (!fast(s, len, &acc, d)) {
+            uint32_t q = 0;
+            const uint64_t chunk = (len + 63) / 64;
+            const uint64_t lo = lane * chunk < len ? lane * chunk : len, hi = lo + chunk < len ? lo + chunk : len;
+            for (uint64_t i = lo; i < hi; i++) {
+                const uint8_t byte = s[i];
+                d[i] = byte;  // the lane's own range of the field: no byte outside it
+                q = (q >> 8) ^ tab[(q ^ byte) & 0xFFu];
+            }
+            q = xdr_shift<32>(a.shift, q, len - hi);
+#pragma unroll
+            for (int k = 1; k < 64; k <<= 1) q ^= __shfl_xor(q, k, 64);
+            acc = xdr_shift<32>(a.shift, acc, len) ^ q;
+        }
+        if (lane == 0)
+            for (uint64_t i = len; i < wire; i++) d[i] = 0;  // xdr_opaque's pad
+        s += len;
+        d += wire;
+    }
+    if (lane == 0) {
+        // (the slot lies in the message's headers, outside every XDR byte)
+        if (!bad) store_be32(const_cast<uint8_t *>(a.buf) + m0 + x.hash_off, acc ^ (uint32_t)a.xorout);
+        if (a.status) a.status[m] = bad ? 1 : 0;
+    }
+}
+
+// Latency layout: xdr_msg_kernel's workgroups.
+__global__ __launch_bounds__(256) void xdr_pack_kernel(XdrPackArgs pa) {
+    const XdrArgs &a = pa.a;
+    __shared__ uint32_t tab[256];
+    tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t m = uniform((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6))); m < a.count; m += nw)
+        xdr_pack_message(a, pa.x, pa.p, m, tab, lane, [](const uint8_t *, uint64_t, uint32_t *, uint8_t *) { return false; });
+}
+
+// Throughput layout: xdr_msg_fast_kernel's workgroups, tables and work queue;
+// fails closed as seal does (the error word here, the statuses by
+// xdr_flag_kernel after the launch).  The copying step loop is instantiated
+// for a table type of this kernel's own, as for unpack (XdrTab32).
+struct XdrPackTab32 : Tab32<false> {};
+template <bool NT>
+__global__ __launch_bounds__(1024, 1) void xdr_pack_fast_kernel(XdrPackArgs pa) {
+    const XdrArgs &a = pa.a;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kXdrMainLds<32> + 256 * sizeof(uint32_t)];
+    __shared__ WgQueue wgq;
+    uint32_t *tab = reinterpret_cast<uint32_t *>(lds + kXdrMainLds<32>);
+    if (threadIdx.x == 0) wg_queue_init(&wgq, a.queue, a.count);
+    const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
+    fill_lds32<false, 1024>(lds, pk);
+    if (threadIdx.x < 256) tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 16u + (threadIdx.x >> 6));
+    const uint32_t nw = gridDim.x * 16u;
+    const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
+    auto fast = [&](const uint8_t *s, uint64_t len, uint32_t *reg, uint8_t *d) -> bool {
+        if (len < kXdrFastMin || len >= (1ull << 31)) return false;
+        *reg = payload32_g64<NT, XdrPackTab32, true, true>(XdrPackTab32{{lds}}, pk, s, len, lane, lc0, lc1, *reg, d);
+        return true;
+    };
+    const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
+                                             [&](uint64_t m) { xdr_pack_message(a, pa.x, pa.p, m, tab, lane, fast); });
+    if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
+}
+
+// mchecksum_gpu_xdr_encoded_sizes / _decoded_sizes: the pre-walks alone, one
+// thread per message -- the INT fields only, with the walks' bounds tests; no
+// tables, no queue, no wait.  a.buf / a.off: the images (ENC) or the messages.
+struct XdrSizeArgs {
+    XdrArgs a;
+    uint64_t pay_off;
+    uint64_t *sizes, *wire;
+};
+template <bool ENC>
+__global__ __launch_bounds__(256) void xdr_sizes_kernel(XdrSizeArgs s) {
+    const XdrArgs &a = s.a;
+    for (uint64_t m = (uint64_t)blockIdx.x * 256 + threadIdx.x; m < a.count; m += (uint64_t)gridDim.x * 256) {
+        const uint64_t pos = a.off[m], end = a.off[m + 1];
+        uint64_t n = 0, w = 0;
+        bool ok = end >= pos;
+        if constexpr (ENC) ok = ok && xdr_encoded_len(a, a.buf + pos, end - pos, &n);
+        else ok = ok && end - pos >= s.pay_off && xdr_decoded_len(a, pos + s.pay_off, end, &n, &w);
+        s.sizes[m] = ok ? n : 0;
+        if (!ENC && s.wire) s.wire[m] = ok ? w : 0;
+        if (a.status) a.status[m] = ok ? 0 : 1;
+    }
 }
 
 }  // namespace
@@ -1732,14 +1944,23 @@ int mchecksum_gpu_seal_core_headers(const char *hash_method, int kind, void *dev
 }
 
 // The XDR entry points' schema check; the fields go into the kernel arguments.
-static int xdr_schema(const mchecksum_xdr_field_t *fields, size_t nfields, XdrArgs *a) {
+// MCHECKSUM_XDR_SINT differs from INT only in the slot the encoder writes: the
+// kernels see INT, and the pack call gets the signed fields as a mask (*sint,
+// one bit per schema entry: kXdrMaxFields is 64).
+static int xdr_schema(const mchecksum_xdr_field_t *fields, size_t nfields, XdrArgs *a, uint64_t *sint = nullptr) {
     if (nfields > kXdrMaxFields) return set_err(MCHECKSUM_GPU_EINVAL, "more than %u schema fields", kXdrMaxFields);
+    static_assert(kXdrMaxFields <= 64, "the signed fields ride in a 64-bit mask");
     for (size_t f = 0; f < nfields; f++) {
-        const uint32_t k = fields[f].kind, z = fields[f].size;
+        uint32_t k = fields[f].kind;
+        const uint32_t z = fields[f].size;
+        if (k == MCHECKSUM_XDR_SINT) {
+            k = MCHECKSUM_XDR_INT;
+            if (sint) *sint |= 1ull << f;
+        }
         const bool ok = (k == MCHECKSUM_XDR_INT && (z == 1 || z == 2 || z == 4 || z == 8)) ||
                         k == MCHECKSUM_XDR_OPAQUE || k == MCHECKSUM_XDR_RAW || k == MCHECKSUM_XDR_OPAQUE_LEN ||
                         k == MCHECKSUM_XDR_RAW_LEN || (k == MCHECKSUM_XDR_SKIP_IF_ZERO && z <= nfields - f - 1);
-        if (!ok) return set_err(MCHECKSUM_GPU_EINVAL, "schema field %zu: bad kind %u / size %u", f, k, z);
+        if (!ok) return set_err(MCHECKSUM_GPU_EINVAL, "schema field %zu: bad kind %u / size %u", f, fields[f].kind, z);
         a->kind[f] = k;
         a->size[f] = z;
     }
@@ -1815,19 +2036,23 @@ int mchecksum_gpu_checksum_xdr(const char *hash_method, const mchecksum_xdr_fiel
     return MCHECKSUM_GPU_OK;
 }
 
+}  // extern "C"
+
 // The kernels of one message operation: the latency layout's, and the
 // throughput layout's with default and non-temporal loads.
+template <class Args>
 struct XdrMsgKernels {
-    void (*lat)(XdrMsgArgs);
-    void (*fast)(XdrMsgArgs);
-    void (*fast_nt)(XdrMsgArgs);
+    void (*lat)(Args);
+    void (*fast)(Args);
+    void (*fast_nt)(Args);
 };
 #define MCK_XDR_MSG_KERNELS(OP) \
-    XdrMsgKernels { xdr_msg_kernel<OP>, xdr_msg_fast_kernel<OP, false>, xdr_msg_fast_kernel<OP, true> }
+    XdrMsgKernels<XdrMsgArgs> { xdr_msg_kernel<OP>, xdr_msg_fast_kernel<OP, false>, xdr_msg_fast_kernel<OP, true> }
 
 // One message call (verify_xdr_messages, seal_xdr_messages,
-// unpack_xdr_messages): the argument checks in the header's order, then
-// checksum_xdr's choice of layout, slot and loads.
+// unpack_xdr_messages, pack_xdr_messages): the argument checks in the
+// header's order, then checksum_xdr's choice of layout, slot and loads.
+// Args: the operation's kernel arguments (XdrMsgArgs; pack: XdrPackArgs).
 struct XdrMsgCall {
     XdrOp op;
     const char *method;
@@ -1841,19 +2066,24 @@ struct XdrMsgCall {
     void *dst = nullptr;
     const uint64_t *dst_off = nullptr;
     uint32_t *mism = nullptr;
+    const void *src = nullptr;  // pack: the images and their table
+    const uint64_t *src_off = nullptr;
 };
 
-static int xdr_msg_call(const XdrMsgCall &mc) {
+template <class Args>
+static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     const size_t count = mc.count;
-    const bool unpack = mc.op == kXdrUnpack;
-    if ((mc.nfields && !mc.fields) || (count && (!mc.buf || !mc.off || (unpack && (!mc.dst || !mc.dst_off)))))
+    const bool unpack = mc.op == kXdrUnpack, pack = mc.op == kXdrPack;
+    if ((mc.nfields && !mc.fields) || (count && (!mc.buf || !mc.off || (unpack && (!mc.dst || !mc.dst_off)) ||
+                                                 (pack && (!mc.src || !mc.src_off)))))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (mc.hash_off > mc.pay_off || mc.pay_off - mc.hash_off < 4)
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
     if ((uint64_t)count > (1ull << 31)) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 messages in one call");
-    XdrMsgArgs ma{};
+    Args ma{};
     XdrArgs &a = ma.a;
-    if (int rc = xdr_schema(mc.fields, mc.nfields, &a)) return rc;
+    uint64_t sint = 0;
+    if (int rc = xdr_schema(mc.fields, mc.nfields, &a, &sint)) return rc;
     Model model;
     const int found = gpu_model(mc.method, &model);
     if (found == -1)
@@ -1880,9 +2110,7 @@ static int xdr_msg_call(const XdrMsgCall &mc) {
     a.status = mc.status;
     xdr_model(model.idx, shift, &a);
     ma.x = XdrMsg{mc.pay_off, mc.hash_off, (uint8_t *)mc.dst, mc.dst_off, mc.mism};
-    const XdrMsgKernels ks = mc.op == kXdrVerify ? MCK_XDR_MSG_KERNELS(kXdrVerify)
-                             : mc.op == kXdrSeal ? MCK_XDR_MSG_KERNELS(kXdrSeal)
-                                                 : MCK_XDR_MSG_KERNELS(kXdrUnpack);
+    if constexpr (std::is_same_v<Args, XdrPackArgs>) ma.p = XdrPack{(const uint8_t *)mc.src, mc.src_off, sint};
     if (!fast) {
         uint64_t blocks = (count + 3) / 4;
         if (blocks > (uint64_t)c->cus * 8) blocks = (uint64_t)c->cus * 8;
@@ -1911,6 +2139,8 @@ static int xdr_msg_call(const XdrMsgCall &mc) {
                        "XDR status launch");
 }
 
+extern "C" {
+
 int mchecksum_gpu_verify_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
                                       const void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
                                       size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
@@ -1918,14 +2148,15 @@ int mchecksum_gpu_verify_xdr_messages(const char *hash_method, const mchecksum_x
     XdrMsgCall mc{kXdrVerify, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
                   dev_status, stream};
     mc.mism = dev_mismatches;
-    return xdr_msg_call(mc);
+    return xdr_msg_call(mc, MCK_XDR_MSG_KERNELS(kXdrVerify));
 }
 
 int mchecksum_gpu_seal_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
                                     void *dev_buf, const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                     size_t hash_offset, uint8_t *dev_status, void *stream) {
     return xdr_msg_call({kXdrSeal, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
-                         hash_offset, dev_status, stream});
+                         hash_offset, dev_status, stream},
+                        MCK_XDR_MSG_KERNELS(kXdrSeal));
 }
 
 int mchecksum_gpu_unpack_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
@@ -1938,7 +2169,59 @@ int mchecksum_gpu_unpack_xdr_messages(const char *hash_method, const mchecksum_x
     mc.dst = dev_dst;
     mc.dst_off = dev_dst_offsets;
     mc.mism = dev_mismatches;
-    return xdr_msg_call(mc);
+    return xdr_msg_call(mc, MCK_XDR_MSG_KERNELS(kXdrUnpack));
+}
+
+int mchecksum_gpu_pack_xdr_messages(const char *hash_method, const mchecksum_xdr_field_t *fields, size_t nfields,
+                                    const void *dev_src, const uint64_t *dev_src_offsets, void *dev_buf,
+                                    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                    size_t hash_offset, uint8_t *dev_status, void *stream) {
+    XdrMsgCall mc{kXdrPack, hash_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, hash_offset,
+                  dev_status, stream};
+    mc.src = dev_src;
+    mc.src_off = dev_src_offsets;
+    return xdr_msg_call(mc, XdrMsgKernels<XdrPackArgs>{xdr_pack_kernel, xdr_pack_fast_kernel<false>,
+                                                       xdr_pack_fast_kernel<true>});
+}
+
+// The size calls: one launch of the pre-walk, nothing of the device context
+// (no tables, no slot), so they can be captured without prepare().
+static int xdr_sizes_call(bool enc, const mchecksum_xdr_field_t *fields, size_t nfields, const void *buf,
+                          const uint64_t *off, size_t count, size_t pay_off, uint64_t *sizes, uint64_t *wire,
+                          uint8_t *status, void *stream) {
+    if ((nfields && !fields) || (count && (!buf || !off || !sizes)))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if ((uint64_t)count > (1ull << 31)) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 messages in one call");
+    XdrSizeArgs s{};
+    if (int rc = xdr_schema(fields, nfields, &s.a)) return rc;
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    s.a.buf = (const uint8_t *)buf;
+    s.a.off = off;
+    s.a.count = count;
+    s.a.status = status;
+    s.pay_off = pay_off;
+    s.sizes = sizes;
+    s.wire = wire;
+    uint64_t blocks = (count + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const hipError_t e = launch_kernel(enc ? xdr_sizes_kernel<true> : xdr_sizes_kernel<false>, dim3((unsigned)blocks),
+                                       dim3(256), (hipStream_t)stream, nullptr, s);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, "XDR sizes kernel launch");
+}
+
+int mchecksum_gpu_xdr_encoded_sizes(const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_src,
+                                    const uint64_t *dev_src_offsets, size_t count, uint64_t *dev_sizes,
+                                    uint8_t *dev_status, void *stream) {
+    return xdr_sizes_call(true, fields, nfields, dev_src, dev_src_offsets, count, 0, dev_sizes, nullptr, dev_status,
+                          stream);
+}
+
+int mchecksum_gpu_xdr_decoded_sizes(const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_buf,
+                                    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                    uint64_t *dev_sizes, uint64_t *dev_wire_sizes, uint8_t *dev_status, void *stream) {
+    return xdr_sizes_call(false, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, dev_sizes,
+                          dev_wire_sizes, dev_status, stream);
 }
 
 }  // extern "C"

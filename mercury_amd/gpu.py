@@ -1003,6 +1003,7 @@ def seal_core_headers(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str =
 
 
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO = 0, 1, 2, 3, 4, 5
+XDR_SINT = 6  # XDR_INT for a signed type: pack_xdr_messages sign-extends it, every other call treats it as XDR_INT
 
 
 def checksum_xdr(method: str, data: torch.Tensor, msg_offsets: torch.Tensor, schema, status: bool = False,
@@ -1125,6 +1126,100 @@ def unpack_xdr_messages(method: str, data: torch.Tensor, msg_offsets: torch.Tens
     if rc != 0:
         _err(rc, "mchecksum_gpu_unpack_xdr_messages")
     return status, mism
+
+
+def pack_xdr_messages(method: str, src: torch.Tensor, src_offsets: torch.Tensor, data: torch.Tensor,
+                      msg_offsets: torch.Tensor, schema, payload_offset: int = 20, hash_offset: int = 16, stream=None,
+                      src_offsets_host=None, offsets_host=None, status=None) -> torch.Tensor:
+    """pack_messages for a Mercury built with XDR encoding, the mirror of
+    unpack_xdr_messages (mchecksum_gpu_pack_xdr_messages): image i =
+    src[src_offsets[i] : src_offsets[i+1]] -- every integer's host-order
+    bytes, every byte array without its pad, in schema order -- is encoded to
+    XDR behind the headers of message i of `data`, hashed in the same read
+    and its CRC stored network-order at msg_offsets[i] + hash_offset.  XDR_SINT
+    fields are sign-extended into their 32-bit word, XDR_INT ones
+    zero-extended.  Returns status (uint8 per message: 1 = the schema does not
+    consume the image exactly or the message is not payload_offset + the
+    encoded length long: nothing of it is written).  The encoded lengths
+    depend on the data (xdr_encoded_sizes computes them), so only the tables'
+    bounds are checked here; with both host tables given the two ranges must
+    not overlap."""
+    _check_device_u8(src, "src")
+    _check_device_u8(data, "data")
+    _check_offsets(src, src_offsets, src_offsets_host)
+    _check_offsets(data, msg_offsets, offsets_host)
+    count = msg_offsets.numel() - 1
+    if count < 0 or src_offsets.numel() != count + 1:
+        raise GpuChecksumError("src_offsets and msg_offsets need the same number (>= 1) of entries")
+    if src_offsets_host is not None and offsets_host is not None and count:
+        import numpy as np
+        so, mo = np.asarray(src_offsets_host, dtype=np.uint64), np.asarray(offsets_host, dtype=np.uint64)
+        s0, d0 = src.data_ptr() + int(so[0]), data.data_ptr() + int(mo[0])
+        if s0 < d0 + int(mo[-1] - mo[0]) and d0 < s0 + int(so[-1] - so[0]):
+            raise GpuChecksumError("the source and destination ranges overlap")
+    status = _sender_status(data, count, status)
+    _same_device(data, src=src, src_offsets=src_offsets, msg_offsets=msg_offsets, status=status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_pack_xdr_messages(method.encode(), _xdr_fields(schema), len(schema), src.data_ptr(),
+                                                    src_offsets.data_ptr(), data.data_ptr(), msg_offsets.data_ptr(),
+                                                    count, payload_offset, hash_offset, status.data_ptr(),
+                                                    _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_xdr_messages")
+    return status
+
+
+def _xdr_sizes_out(data: torch.Tensor, count: int):
+    return (torch.empty(max(count, 0), dtype=torch.int64, device=data.device),
+            torch.empty(max(count, 0), dtype=torch.uint8, device=data.device))
+
+
+def xdr_encoded_sizes(src: torch.Tensor, src_offsets: torch.Tensor, schema, stream=None, src_offsets_host=None):
+    """The XDR length pack_xdr_messages would write for each image
+    (mchecksum_gpu_xdr_encoded_sizes), computed on the device from the image's
+    integers.  Returns (sizes int64, status uint8): 0 and status 1 where the
+    schema does not consume the image exactly.  torch.cumsum of payload_offset
+    + sizes is the message table."""
+    _check_device_u8(src, "src")
+    _check_offsets(src, src_offsets, src_offsets_host)
+    _same_device(src, src_offsets=src_offsets)
+    count = src_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("src_offsets needs at least one entry")
+    sizes, status = _xdr_sizes_out(src, count)
+    with _on(src):
+        rc = _lib().mchecksum_gpu_xdr_encoded_sizes(_xdr_fields(schema), len(schema), src.data_ptr(),
+                                                    src_offsets.data_ptr(), count, sizes.data_ptr(), status.data_ptr(),
+                                                    _stream_handle(stream, src.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_xdr_encoded_sizes")
+    return sizes, status
+
+
+def xdr_decoded_sizes(data: torch.Tensor, msg_offsets: torch.Tensor, schema, payload_offset: int = 20, stream=None,
+                      offsets_host=None):
+    """The decoded length of each XDR-mode message -- what its slot in
+    unpack_xdr_messages' destination table must be -- and the XDR bytes the
+    schema consumed from payload_offset on (mchecksum_gpu_xdr_decoded_sizes).
+    Returns (sizes int64, wire_sizes int64, status uint8): zeros and status 1
+    where the message is shorter than payload_offset or the schema runs past
+    it."""
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    _same_device(data, msg_offsets=msg_offsets)
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    sizes, status = _xdr_sizes_out(data, count)
+    wire = torch.empty_like(sizes)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_xdr_decoded_sizes(_xdr_fields(schema), len(schema), data.data_ptr(),
+                                                    msg_offsets.data_ptr(), count, payload_offset, sizes.data_ptr(),
+                                                    wire.data_ptr(), status.data_ptr(),
+                                                    _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_xdr_decoded_sizes")
+    return sizes, wire, status
 
 
 def fill_splitmix(t: torch.Tensor, seed: int, first_word: int = 0, stream=None) -> torch.Tensor:
