@@ -605,6 +605,102 @@ mchecksum_gpu_verify_segments(const char *hash_method,
     size_t work_size, const void *dev_expected, uint8_t *dev_status,
     uint32_t *dev_mismatches, void *stream);
 
+/* Per-field pack and unpack of RPC messages: pack_messages / unpack_messages
+ * with a segment list per message in place of one contiguous range -- what
+ * HG_PROC_TYPE does field by field (copy the field, feed the same bytes to
+ * mchecksum_update, src/mercury_proc.h:124-143,162-181) before hg_set_struct
+ * stores and hg_get_struct compares the hash (src/mercury.c:565-573,699-707).
+ * One pass over the payload bytes each; CRC-32C.
+ *
+ * Tables.  Message j = dev_buf[dev_msg_offsets[j], dev_msg_offsets[j+1]): nobj
+ * + 1 non-decreasing entries.  Its fields are segments [dev_obj_first[j],
+ * dev_obj_first[j+1]) of the segment table, in order, under checksum_segments'
+ * rules: segments outside every object are neither read nor written, an empty
+ * segment contributes nothing.  N_j = the sum of object j's segment lengths.
+ * Message j fits iff
+ *   dev_msg_offsets[j+1] - dev_msg_offsets[j] == payload_offset + N_j
+ * (a message shorter than payload_offset never fits; an object with no bytes
+ * fits a message of exactly payload_offset bytes, and its value is the CRC of
+ * the empty message).
+ *
+ * pack: a fitting message's segments are copied, concatenated, to
+ * dev_buf[dev_msg_offsets[j] + payload_offset, dev_msg_offsets[j+1]) and hashed
+ * in the same read; the CRC-32C is stored big-endian in the 4 bytes at
+ * dev_msg_offsets[j] + hash_offset, and dev_status[j] = 0.  A message that does
+ * not fit gets status 1, and no byte of it is written.  The call writes exactly
+ * the payload bytes and the 4 hash bytes of fitting messages -- no other header
+ * byte (the caller fills those), nothing before, between or after messages --
+ * and never writes segment memory.  dev_status may be NULL.
+ *
+ * unpack: a fitting message's payload is spread over its segments in order
+ * (dev_seg_addr are destinations: exactly dev_seg_len[s] bytes of each are
+ * written), hashed in the same read and compared with the network-order u32 at
+ * dev_msg_offsets[j] + hash_offset.  Status 0 on a match; status 1 and one
+ * mismatch when the CRC differs -- the segments then hold the bytes AS
+ * RECEIVED, as after unpack_messages: look at the status before the bytes.  A
+ * message that does not fit gets status 1 and one mismatch, and no segment byte
+ * of it is written.  dev_buf is never written.  Either of dev_status and
+ * dev_mismatches may be NULL; *dev_mismatches is added to (the caller zeroes
+ * it).
+ *
+ * Memory.  The side that is read must be readable to the next 16-byte boundary
+ * (each segment for pack; dev_buf after its last message byte for unpack).
+ * Written ranges must not overlap one another or anything read; the library
+ * cannot check that (the tables are on the device).
+ *
+ * Arguments, in this order: MCHECKSUM_GPU_EINVAL for a NULL pointer (the
+ * segment arrays only when nseg > 0; dev_status and dev_mismatches are
+ * optional), hash_offset + 4 > payload_offset, nobj > 2^31, nseg >= 2^32, a
+ * workspace smaller than mchecksum_gpu_segment_messages_work_size(nseg, nobj)
+ * or not 8-byte aligned; then the method -- crc32c only, as pack_messages:
+ * every other name is MCHECKSUM_GPU_EMETHOD, on a box without a GPU too --;
+ * then the device.  nobj == 0 passes the same checks except those of the
+ * buffers: it needs none, the workspace included, and makes no launch.
+ *
+ * Workspace: mchecksum_gpu_segment_messages_work_size(nseg, nobj) >=
+ * mchecksum_gpu_segments_work_size(nseg): that workspace plus, per object, the
+ * accumulator word of the pass and the fit gate; SIZE_MAX beyond the caps.  One
+ * workspace per concurrent call.
+ *
+ * Asynchronous and stream-ordered; capture-safe after
+ * mchecksum_gpu_prepare("crc32c").  A replay scans the tables again: segment
+ * lengths, the message table and the contents may all change between replays.
+ *
+ * Fail closed, as verify_segments: a call whose scan gave up writes nothing --
+ * no payload byte, no hash byte, no segment byte --, sets every status to 1
+ * and adds 1 to the error word, once; unpack also adds nobj to
+ * *dev_mismatches.  The launch after the chunk pass reads the call's fault
+ * state before it stores or compares any value, so a half-accumulated CRC is
+ * never sealed or accepted.
+ *
+ * Cost: four launches (scan, fit, chunk pass, seal or compare); the chunk pass
+ * gives a wave to every field (every 256 KiB chunk of it).  Against the two
+ * calls it replaces over the same tables (gather_segments + seal_messages;
+ * verify_messages + scatter_segments), measured on an MI355X (DESIGN.md 4.20,
+ * one run, medians): 8192 messages of 64 KiB in 4 segments, pack 0.56x and
+ * unpack 0.74x the time of the pair; 65536 messages of 4 KiB in 3 unequal
+ * fields at odd addresses, 0.83x both ways -- there the wave per field, not
+ * the second read, is most of either route. */
+MCHECKSUM_PUBLIC size_t
+mchecksum_gpu_segment_messages_work_size(size_t nseg, size_t nobj);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_segment_messages(const char *hash_method,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first, size_t nobj,
+    void *dev_buf, const uint64_t *dev_msg_offsets,
+    size_t payload_offset, size_t hash_offset,
+    void *dev_work, size_t work_size, uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_segment_messages(const char *hash_method,
+    const void *dev_buf, const uint64_t *dev_msg_offsets, size_t nobj,
+    size_t payload_offset, size_t hash_offset,
+    const uint64_t *dev_seg_addr, const uint64_t *dev_seg_len, size_t nseg,
+    const uint64_t *dev_obj_first,
+    void *dev_work, size_t work_size,
+    uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
+
 /* Batched check of Mercury core headers for received
  * messages in device memory: message i = dev_buf[dev_msg_offsets[i],
  * dev_msg_offsets[i+1]) starts with the 16-byte core header that

@@ -33,7 +33,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_update_scatter_segments", "mchecksum_gpu_verify_segments", "mchecksum_gpu_state_verify",
                "mchecksum_gpu_verify_xdr_messages", "mchecksum_gpu_seal_xdr_messages",
                "mchecksum_gpu_unpack_xdr_messages", "mchecksum_gpu_pack_xdr_messages",
-               "mchecksum_gpu_xdr_encoded_sizes", "mchecksum_gpu_xdr_decoded_sizes")
+               "mchecksum_gpu_xdr_encoded_sizes", "mchecksum_gpu_xdr_decoded_sizes",
+               "mchecksum_gpu_segment_messages_work_size", "mchecksum_gpu_pack_segment_messages",
+               "mchecksum_gpu_unpack_segment_messages")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -108,6 +110,20 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_verify_segments.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                                 c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
     L.mchecksum_gpu_verify_segments.restype = c_int
+    L.mchecksum_gpu_segment_messages_work_size.argtypes = [c_size_t, c_size_t]
+    L.mchecksum_gpu_segment_messages_work_size.restype = c_size_t
+    # (method, seg_addr, seg_len, nseg, obj_first, nobj, buf, msg_offsets, payload_offset, hash_offset, work,
+    #  work_size, status, stream)
+    L.mchecksum_gpu_pack_segment_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                      c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t,
+                                                      c_void_p, c_void_p]
+    L.mchecksum_gpu_pack_segment_messages.restype = c_int
+    # (method, buf, msg_offsets, nobj, payload_offset, hash_offset, seg_addr, seg_len, nseg, obj_first, work,
+    #  work_size, status, mismatches, stream)
+    L.mchecksum_gpu_unpack_segment_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t,
+                                                        c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                        c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_unpack_segment_messages.restype = c_int
     L.mchecksum_gpu_verify_core_headers.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                                     c_void_p, c_void_p]
     L.mchecksum_gpu_verify_core_headers.restype = c_int

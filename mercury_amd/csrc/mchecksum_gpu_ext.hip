@@ -911,6 +911,117 @@ __global__ __launch_bounds__(1024, 1) void seg_copy_kernel(SegCopyArgs ca) {
     }
 }
 
+// The message calls (mchecksum_gpu_pack_segment_messages, _unpack_segment_
+// messages; CRC-32C): object j's segments are the fields of message j, the
+// per-field form of pack_messages / unpack_messages (HG_PROC_TYPE copies a
+// field and feeds the same bytes to mchecksum_update, src/mercury_proc.h:
+// 124-143,162-181).  The copying pass above with the messages' payloads as
+// the contiguous side -- c.flat = dev_buf + payload_offset, c.starts = the
+// message table -- in a kernel of its own (the plain copying kernels keep
+// their code) between two thread-per-object launches:
+//   before: the fit of message j (seg_plan.h, seg_msg_gate: from the scan's P
+//           and the message table) into gate[j], and the object's accumulator
+//           word (c.s.out, a word per object behind the scan's workspace:
+//           seg_msg_layout) zeroed;
+//   the pass: seg_copy_kernel<32, DIR>'s walk and loop; no chunk of a message
+//           that does not fit is loaded or stored;
+//   after:  the call's fault state first, as verify_segments' compare; then
+//           pack stores the finalised value big-endian in the header's hash
+//           slot (byte by byte: the slot has no alignment), unpack compares it
+//           with the word there and counts.  A gated message gets status 1
+//           and, on unpack, one mismatch.
+// The CRC-32C pass walks static ranges: only the scan can give up.
+struct SegMsgArgs {
+    SegCopyArgs c;
+    uint8_t *gate;          // nobj bytes of the workspace
+    uint8_t *buf;           // the messages (unpack only reads them)
+    const uint64_t *off;    // nobj + 1 message offsets
+    uint64_t pay_off, hash_off;
+    uint8_t *status;
+    uint32_t *mism;
+    uint32_t init, xorout;
+};
+
+__global__ __launch_bounds__(256) void seg_msg_pre_kernel(SegMsgArgs ma) {
+    const SegArgs &a = ma.c.s;
+    uint32_t *acc = reinterpret_cast<uint32_t *>(a.out);
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < a.nobj; j += (uint64_t)gridDim.x * 256) {
+        const uint64_t f0 = a.first[j], f1 = a.first[j + 1];
+        const bool ok = mck::seg_msg_range_ok(f0, f1, a.nseg);
+        const uint64_t p0 = ok ? a.w.P[f0] : 0, p1 = ok ? a.w.P[f1] : 0;
+        acc[j] = 0;
+        ma.gate[j] = mck::seg_msg_gate(ok, p0, p1, ma.off[j], ma.off[j + 1], ma.pay_off);
+    }
+}
+
+template <int DIR>
+__global__ __launch_bounds__(1024, 1) void seg_msg_copy_kernel(SegMsgArgs ma) {
+    static_assert(DIR == mck::kSegGather || DIR == mck::kSegScatter, "no such direction");
+    const SegArgs &a = ma.c.s;
+    __shared__ __attribute__((aligned(16))) uint8_t lds_raw[kL32Bytes];
+    constexpr int kWPB = 1024 / 64;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWPB + (threadIdx.x >> 6));
+    const uint32_t nw = gridDim.x * kWPB;
+    const uint64_t nchunks = uniform(a.w.C[a.nseg]);
+    // hash nothing and, ahead of the first store below, write nothing
+    if (scan_gave_up(a)) return;
+    const bool nt = uniform(a.w.P[a.nseg]) >= kSegNtBytes;  // as seg_kernel
+    const uint64_t flat = reinterpret_cast<uint64_t>(ma.c.flat);
+    const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
+    const crc32_shift_pack_t *sp = reinterpret_cast<const crc32_shift_pack_t *>(a.shift);
+    [[clang::always_inline]] fill_lds32<false, 1024>(lds_raw, pk);  // (as in seg_copy_kernel)
+    __syncthreads();
+    const Tab32<false> lds{lds_raw};
+    const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
+    const uint32_t init = pk->init;
+    ChunkWalk walk(a, wave, nw, nchunks);
+    SegChunk k;
+    while (walk.next(&k)) {
+        if (!k.in) continue;           // (a chunk the walk could not place is stored nowhere)
+        if (ma.gate[k.obj]) continue;  // the message does not fit: none of its bytes moves
+        const mck::SegCopyAddr ad = mck::seg_copy_addr(DIR, k.addr, flat, ma.c.starts[k.obj], k.obj_off);
+        const uint8_t *q = reinterpret_cast<const uint8_t *>(ad.load);
+        uint8_t *d = reinterpret_cast<uint8_t *>(ad.store);
+        const uint64_t n = k.n;
+        const uint32_t reg = k.head && n >= 4 ? init : 0u;
+        const uint32_t x = nt ? payload32_g64<true, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d)
+                              : payload32_g64<false, Tab32<false>, true, true>(lds, pk, q, n, lane, lc0, lc1, reg, d);
+        seg_emit<32>(pk, sp, a.out, init, x, k, lane);
+    }
+}
+
+// DIR: kSegGather = pack (seal), kSegScatter = unpack (compare)
+template <int DIR>
+__global__ __launch_bounds__(256) void seg_msg_post_kernel(SegMsgArgs ma) {
+    const SegArgs &a = ma.c.s;
+    const uint64_t claim = ld_relaxed(a.w.fault_claim);
+    const bool faulted = mck::seg_call_faulted(claim, claim, scan_key(a.epoch, ld_relaxed(a.w.gen) - 1));
+    const uint32_t *acc = reinterpret_cast<const uint32_t *>(a.out);
+    uint32_t nbad = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < a.nobj; j += (uint64_t)gridDim.x * 256) {
+        const uint8_t gate = ma.gate[j];
+        const uint32_t v = mck_seg_value32(faulted ? 0u : acc[j], ma.init, ma.xorout, 0);
+        if constexpr (DIR == mck::kSegGather) {
+            if (mck::seg_msg_seal_decide(faulted, gate, ma.status, j)) {
+                uint8_t *h = ma.buf + ma.off[j] + ma.hash_off;
+                h[0] = (uint8_t)(v >> 24);
+                h[1] = (uint8_t)(v >> 16);
+                h[2] = (uint8_t)(v >> 8);
+                h[3] = (uint8_t)v;
+            }
+        } else {
+            uint32_t want = 0;
+            if (mck::seg_msg_compares(faulted, gate)) {
+                const uint8_t *h = ma.buf + ma.off[j] + ma.hash_off;
+                want = (uint32_t)h[0] << 24 | (uint32_t)h[1] << 16 | (uint32_t)h[2] << 8 | h[3];
+            }
+            nbad += mck::seg_msg_open_decide(faulted, gate, v, want, ma.status, j);
+        }
+    }
+    if constexpr (DIR == mck::kSegScatter) add_mismatches(ma.mism, nbad);  // once per workgroup; no counter: nothing added
+}
+
 // --------------------------------------------------------- core headers ----
 //
 // Wire layout (hg_core_header_*_proc, src/mercury_core_header.c:175-289; the
@@ -1715,14 +1826,106 @@ struct SegCall {
     const void *expected = nullptr;
     uint8_t *status = nullptr;
     uint32_t *mism = nullptr;
+    // a message call (pack / unpack_segment_messages): flat holds the
+    // messages, starts is their nobj + 1 offsets, no out
+    bool msg = false;
+    size_t pay_off = 0, hash_off = 0;
 };
+
+// A message call: its own argument order (the method is an argument, checked
+// ahead of the device, as pack_messages does), then the scan, the fit launch,
+// the gated copying pass and the seal / compare launch.
+static int seg_msg_call(const SegCall &sc) {
+    const size_t nseg = sc.nseg, nobj = sc.nobj;
+    // an empty batch needs no buffers, the workspace included
+    if (nobj && (!sc.obj_first || !sc.work || !sc.flat || !sc.starts || (nseg && (!sc.seg_addr || !sc.seg_len))))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (sc.hash_off + 4 > sc.pay_off || sc.pay_off > (1u << 30))
+        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
+    if ((uint64_t)nobj > mck::kMaxMsgObjs) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 messages in one call");
+    if ((uint64_t)nseg > mck::kMaxVerifySegs)
+        return set_err(MCHECKSUM_GPU_EINVAL, "the message calls take fewer than 2^32 segments in one call");
+    mck::SegMsgLayout ml{};
+    (void)mck::seg_msg_layout(nseg, nobj, &ml);  // (within both caps)
+    if (nobj && (sc.work_size < ml.bytes || (uintptr_t)sc.work % 8))
+        return set_err(MCHECKSUM_GPU_EINVAL,
+                       "workspace smaller than mchecksum_gpu_segment_messages_work_size() or unaligned");
+    Model m;
+    int rc = resolve_model(sc.method, &m);
+    if (rc) return rc;
+    if (strcmp(mck_models[m.idx].name, "crc32c") != 0)
+        return set_err(MCHECKSUM_GPU_EMETHOD, "the message calls on segment lists take crc32c only");
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    DevCtx *c = nullptr;
+    const void *pack = nullptr, *shift = nullptr;
+    rc = device_ctx(&c);
+    if (!rc) rc = get_pack(c, m.idx, CRC_GPU_MAX_LOG2G, &pack);
+    if (!rc) rc = get_ext(c, m.idx, &shift);
+    if (rc) return rc;
+    if (nobj == 0) return MCHECKSUM_GPU_OK;
+    uint64_t *const work = static_cast<uint64_t *>(sc.work);
+    SegArgs a{};
+    a.addr = sc.seg_addr;
+    a.len = sc.seg_len;
+    a.nseg = nseg;
+    a.first = sc.obj_first;
+    a.nobj = nobj;
+    a.w = seg_work(sc.work, nseg);
+    a.w.map_cap = 0;  // (only the CRC-64 queue pass reads the map)
+    a.out = work + ml.acc;
+    a.pack = pack;
+    a.shift = shift;
+    a.err_word = error_word();
+    a.epoch = scan_epoch();
+    const crc_rmodel_t rm = gpu_rmodel(m.idx);
+    ScanArgs sa{};
+    sa.len = sc.seg_len;
+    sa.addr = sc.seg_addr;
+    sa.nseg = nseg;
+    sa.epoch = a.epoch;
+    sa.first = sc.obj_first;
+    sa.nobj = nobj;
+    sa.w = a.w;
+    sa.w.obj = nullptr;  // (CRC-32C: no object records)
+    sa.out = nullptr;    // (the fit launch zeroes the accumulator words)
+    sa.width = 32;
+    sa.preset = rm.rinit ^ rm.xorout;
+    sa.err_word = a.err_word;
+    sa.fault_block = scan_fault_block();
+    const hipStream_t st = (hipStream_t)sc.stream;
+    hipError_t e = launch_kernel(seg_scan, dim3((unsigned)seg_scan_blocks(nseg)), dim3(kScanThreads), st, nullptr, sa);
+    if (e != hipSuccess) return hip_err(e, "segment scan launch");
+    uint8_t *const buf = static_cast<uint8_t *>(sc.flat);
+    const SegMsgArgs ma{{a, buf + sc.pay_off, sc.starts},
+                        reinterpret_cast<uint8_t *>(work + ml.gate),
+                        buf,
+                        sc.starts,
+                        sc.pay_off,
+                        sc.hash_off,
+                        sc.status,
+                        sc.mism,
+                        (uint32_t)rm.rinit,
+                        (uint32_t)rm.xorout};
+    e = launch_kernel(seg_msg_pre_kernel, dim3(seg_elem_grid(nobj)), dim3(256), st, nullptr, ma);
+    if (e != hipSuccess) return hip_err(e, "segment message fit launch");
+    const bool gather = sc.dir == mck::kSegGather;
+    SlotRef sr;  // (no work queue: the CRC-32C pass walks static ranges)
+    rc = launch_slot(c, sr, gather ? seg_msg_copy_kernel<mck::kSegGather> : seg_msg_copy_kernel<mck::kSegScatter>,
+                     (unsigned)c->cus, 1024, sc.stream, ma, "segment message kernel launch");
+    if (rc != MCHECKSUM_GPU_OK) return rc;
+    e = launch_kernel(gather ? seg_msg_post_kernel<mck::kSegGather> : seg_msg_post_kernel<mck::kSegScatter>,
+                      dim3(seg_elem_grid(nobj)), dim3(256), st, nullptr, ma);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, gather ? "segment message seal launch" : "segment message compare launch");
+}
 
 // The front of the segment entry points: the argument checks, the scan launch
 // and the chunk pass -- seg_kernel, or for a copying call seg_copy_kernel
 // under the same launch policy.  An update call seeds the states between the
 // two (seg_pre_kernel) and has the same chunk pass XOR into them; verify runs
-// the chunk pass on words of the workspace and the compare after it.
+// the chunk pass on words of the workspace and the compare after it.  (The
+// message calls: seg_msg_call.)
 static int seg_call(const SegCall &sc) {
+    if (sc.msg) return seg_msg_call(sc);
     const bool copy = sc.dir != kSegHashOnly, verify = sc.mode == SegCall::kVerify;
     const size_t nseg = sc.nseg, nobj = sc.nobj;
     if (!sc.obj_first || (nobj && !(verify ? sc.expected : sc.out)) || (nseg && (!sc.seg_addr || !sc.seg_len)) ||
@@ -1889,6 +2092,42 @@ int mchecksum_gpu_verify_segments(const char *hash_method, const uint64_t *dev_s
     sc.expected = dev_expected;
     sc.status = dev_status;
     sc.mism = dev_mismatches;
+    return seg_call(sc);
+}
+
+size_t mchecksum_gpu_segment_messages_work_size(size_t nseg, size_t nobj) { return seg_msg_work_bytes(nseg, nobj); }
+
+int mchecksum_gpu_pack_segment_messages(const char *hash_method, const uint64_t *dev_seg_addr,
+                                        const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
+                                        size_t nobj, void *dev_buf, const uint64_t *dev_msg_offsets,
+                                        size_t payload_offset, size_t hash_offset, void *dev_work, size_t work_size,
+                                        uint8_t *dev_status, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, nullptr, stream};
+    sc.dir = mck::kSegGather;
+    sc.flat = dev_buf;
+    sc.starts = dev_msg_offsets;
+    sc.status = dev_status;
+    sc.msg = true;
+    sc.pay_off = payload_offset;
+    sc.hash_off = hash_offset;
+    return seg_call(sc);
+}
+
+int mchecksum_gpu_unpack_segment_messages(const char *hash_method, const void *dev_buf,
+                                          const uint64_t *dev_msg_offsets, size_t nobj, size_t payload_offset,
+                                          size_t hash_offset, const uint64_t *dev_seg_addr,
+                                          const uint64_t *dev_seg_len, size_t nseg, const uint64_t *dev_obj_first,
+                                          void *dev_work, size_t work_size, uint8_t *dev_status,
+                                          uint32_t *dev_mismatches, void *stream) {
+    SegCall sc{hash_method, dev_seg_addr, dev_seg_len, nseg, dev_obj_first, nobj, dev_work, work_size, nullptr, stream};
+    sc.dir = mck::kSegScatter;
+    sc.flat = const_cast<void *>(dev_buf);
+    sc.starts = dev_msg_offsets;
+    sc.status = dev_status;
+    sc.mism = dev_mismatches;
+    sc.msg = true;
+    sc.pay_off = payload_offset;
+    sc.hash_off = hash_offset;
     return seg_call(sc);
 }
 

@@ -237,6 +237,69 @@ MCK_HOST_DEVICE_INLINE uint32_t seg_verify_decide(bool faulted, uint64_t value, 
     return bad;
 }
 
+// The message calls (pack_segment_messages, unpack_segment_messages): object
+// j's segments are the fields of message j = buf[offsets[j], offsets[j + 1]),
+// whose payload starts payload_offset bytes in.  The calls take more objects
+// than the workspace of a plain segment call has room for, so theirs is that
+// workspace (seg_work_layout, unchanged: the scan writes it as ever) with two
+// per-object regions behind it: the accumulator words (u32, CRC-32C only) the
+// chunk pass XORs into, indexed by the object, and the fit gates (a byte
+// each, non-zero: the message does not fit, its chunks are skipped).
+constexpr uint64_t kMaxMsgObjs = 1ull << 31;
+struct SegMsgLayout {
+    uint64_t acc;   // 8-byte word offset of the nobj u32 accumulator words
+    uint64_t gate;  // 8-byte word offset of the nobj gate bytes
+    uint64_t bytes;
+};
+MCK_HOST_DEVICE_INLINE bool seg_msg_layout(uint64_t nseg, uint64_t nobj, SegMsgLayout *m) {
+    if (nseg > kMaxVerifySegs || nobj > kMaxMsgObjs) return false;
+    m->acc = (seg_work_layout(nseg).bytes + 7) / 8;
+    m->gate = m->acc + (nobj + 1) / 2;
+    m->bytes = 8 * (m->gate + (nobj + 7) / 8);
+    return true;
+}
+// what mchecksum_gpu_segment_messages_work_size returns
+MCK_HOST_DEVICE_INLINE size_t seg_msg_work_bytes(uint64_t nseg, uint64_t nobj) {
+    SegMsgLayout m{};
+    return seg_msg_layout(nseg, nobj, &m) ? (size_t)m.bytes : SIZE_MAX;
+}
+
+// The fit rule: message [m0, m1) holds payload_offset header bytes and then
+// exactly the object's n bytes.  A table that runs backwards, or a message
+// shorter than its headers, never fits.
+MCK_HOST_DEVICE_INLINE bool seg_msg_fits(uint64_t m0, uint64_t m1, uint64_t payload_offset, uint64_t n) {
+    return m1 >= m0 && m1 - m0 >= payload_offset && m1 - m0 - payload_offset == n;
+}
+// The gate of object j, from the words the launch ahead of the chunk pass
+// loaded: f0 = first[j], f1 = first[j + 1] (a range outside the segment table
+// has no prefix to read: gated; p0 = P[f0], p1 = P[f1] are read only inside
+// it, by the caller).
+MCK_HOST_DEVICE_INLINE bool seg_msg_range_ok(uint64_t f0, uint64_t f1, uint64_t nseg) {
+    return f0 <= f1 && f1 <= nseg;
+}
+MCK_HOST_DEVICE_INLINE uint8_t seg_msg_gate(bool range_ok, uint64_t p0, uint64_t p1, uint64_t m0, uint64_t m1,
+                                            uint64_t payload_offset) {
+    return range_ok && p1 >= p0 && seg_msg_fits(m0, m1, payload_offset, p1 - p0) ? 0 : 1;
+}
+
+// After the chunk pass, per message.  Pack: whether the value is sealed into
+// the header -- never after a faulted call (the value may be half
+// accumulated), never for a gated message (nothing of it was written) --;
+// status = 1 where it is not.  Returns the seal decision.
+MCK_HOST_DEVICE_INLINE bool seg_msg_seal_decide(bool faulted, uint8_t gate, uint8_t *status, uint64_t j) {
+    const bool seal = !faulted && gate == 0;
+    if (status) status[j] = seal ? 0 : 1;
+    return seal;
+}
+// Unpack: whether the header word may be read and compared at all (a gated
+// message may be shorter than its headers), and the verdict -- verify_segments'
+// rule, a gated message counting as a faulted one: status 1, one mismatch.
+MCK_HOST_DEVICE_INLINE bool seg_msg_compares(bool faulted, uint8_t gate) { return !faulted && gate == 0; }
+MCK_HOST_DEVICE_INLINE uint32_t seg_msg_open_decide(bool faulted, uint8_t gate, uint64_t value, uint64_t header,
+                                                    uint8_t *status, uint64_t j) {
+    return seg_verify_decide(!seg_msg_compares(faulted, gate), value, header, status, j);
+}
+
 }  // namespace mck
 
 #endif  // MCK_SEG_PLAN_H

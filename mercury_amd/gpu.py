@@ -663,8 +663,9 @@ class SegmentBatch:
         self._span = (int(first[0]), int(first[-1]))
         self.meta = torch.from_numpy(np.concatenate([np.asarray(addr, dtype=np.uint64).view(np.int64),
                                                      np.asarray(lens, dtype=np.int64), first])).to(self.device)
-        self.work = torch.empty((_lib().mchecksum_gpu_segments_work_size(self.nseg) + 7) // 8, dtype=torch.int64,
-                                device=self.device)
+        # (the message calls' size: the segment calls' plus two words' worth per object)
+        need = _lib().mchecksum_gpu_segment_messages_work_size(self.nseg, self.nobj)
+        self.work = torch.empty((need + 7) // 8, dtype=torch.int64, device=self.device)
         self._starts = None  # the starts table of the last gather / scatter: alive for a captured call's replays
         self._last = None  # (stream handle, its torch stream, event after the call or None) of the last call
 
@@ -873,6 +874,111 @@ class SegmentBatch:
                                                                  _ptr(status), _ptr(mism), h))
         return status, mism
 
+    def _messages(self, data, msg_offsets, msg_offsets_host, payload_offset: int):
+        """Checks of a message call's buffer and message table; returns the
+        device table (int64, nobj + 1 entries).  A host sequence, or
+        msg_offsets_host beside a device tensor, is checked first (ValueError,
+        no device needed): non-decreasing, inside `data`, and -- for the
+        messages that fit, the only ones touched -- _check_segment_tables'
+        rules on the payload ranges; a device tensor alone is trusted, as in
+        the C ABI."""
+        import numpy as np
+        if not isinstance(data, torch.Tensor):
+            raise GpuChecksumError("data must be a tensor")
+        mh = msg_offsets_host if isinstance(msg_offsets, torch.Tensor) else msg_offsets
+        if mh is not None:
+            mh = np.asarray(mh)
+            if mh.ndim != 1 or len(mh) != self.nobj + 1:
+                raise ValueError(f"the message table needs {self.nobj + 1} entries, one more than objects")
+            mh = mh.astype(np.uint64).astype(np.int64)
+            if np.any(mh < 0) or np.any(mh[1:] < mh[:-1]):
+                raise ValueError("message offsets must be non-negative and non-decreasing")
+            if int(mh[-1]) > data.numel() * data.element_size():
+                raise ValueError("message offsets extend past the end of data")
+            first = np.asarray(self._first, dtype=np.int64)
+            P = np.concatenate([[0], np.cumsum(self._lens)]).astype(np.int64)
+            fits = mh[1:] - mh[:-1] == payload_offset + P[first[1:]] - P[first[:-1]]
+            lens = np.asarray(self._lens, dtype=np.int64).copy()
+            for j in np.nonzero(~fits)[0]:  # a message that does not fit is no range
+                lens[first[j]:first[j + 1]] = 0
+            _check_segment_tables(data.numel() * data.element_size(), data.data_ptr(), mh[:-1] + payload_offset,
+                                  self._addr, lens, first)
+        _check_device_u8(data, "data")
+        if data.device != self.device:
+            raise GpuChecksumError(f"data must be on {self.device}")
+        if isinstance(msg_offsets, torch.Tensor):
+            if (msg_offsets.dtype != torch.int64 or msg_offsets.device != self.device
+                    or not msg_offsets.is_contiguous() or msg_offsets.numel() != self.nobj + 1):
+                raise GpuChecksumError(f"msg_offsets must be a contiguous int64 tensor of nobj + 1 elements on "
+                                       f"{self.device}")
+            return msg_offsets
+        return torch.from_numpy(np.ascontiguousarray(mh, dtype=np.int64)).to(self.device)
+
+    def _msg_work(self):
+        """The message calls' workspace: the scan's plus two words' worth per
+        object (mchecksum_gpu_segment_messages_work_size)."""
+        need = _lib().mchecksum_gpu_segment_messages_work_size(self.nseg, self.nobj)
+        if self.work.numel() * 8 < need:
+            raise GpuChecksumError("the batch's workspace is too small for a message call")
+        return self.work
+
+    def pack_messages(self, data: torch.Tensor, msg_offsets, payload_offset: int = 20, hash_offset: int = 16,
+                      status=None, stream=None, msg_offsets_host=None) -> torch.Tensor:
+        """pack_messages field by field, in one pass: object j's segments, in
+        order and at their current lengths, are copied behind the headers of
+        message j (data[msg_offsets[j] + payload_offset : msg_offsets[j+1]])
+        and their CRC-32C is stored network-order at msg_offsets[j] +
+        hash_offset -- HG_PROC_TYPE per field, then hg_set_struct.  Returns
+        status (uint8 per message: 1 = the message is not exactly
+        payload_offset + N_j bytes long; nothing of it is written).  Only
+        payload and hash bytes of fitting messages are written; the caller
+        fills the other header bytes.  msg_offsets: nobj + 1 byte offsets, a
+        host sequence (uploaded here) or a device int64 tensor (for a captured
+        call, and to reuse one table); host tables are checked before any
+        launch (_messages).  status: None allocates, False leaves it out, a
+        tensor is reused."""
+        mo = self._messages(data, msg_offsets, msg_offsets_host, payload_offset)
+        if status is not False:
+            status = _sender_status(data, self.nobj, status)
+            if status.device != self.device:
+                raise GpuChecksumError(f"status must be on {self.device}")
+        work = self._msg_work()
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_pack_segment_messages", stream,
+                  lambda h: _lib().mchecksum_gpu_pack_segment_messages(b"crc32c", base, base + 8 * n, n, base + 16 * n,
+                                                                       self.nobj, data.data_ptr(), mo.data_ptr(),
+                                                                       payload_offset, hash_offset, work.data_ptr(),
+                                                                       work.numel() * 8, _ptr(status), h))
+        self._starts = mo  # (kept alive for a captured call's replays)
+        return status
+
+    def unpack_messages(self, data: torch.Tensor, msg_offsets, payload_offset: int = 20, hash_offset: int = 16,
+                        status=None, mismatches=None, stream=None, msg_offsets_host=None):
+        """The receiver's mirror of pack_messages: message j's payload is
+        spread over object j's segments in order -- the segment tensors are
+        written, exactly their current lengths -- and its CRC-32C is compared
+        with the network-order u32 at msg_offsets[j] + hash_offset
+        (HG_PROC_TYPE per field on HG_DECODE, then hg_get_struct).  Returns
+        (status, mismatches) like verify_messages: status 1 = the CRC differs
+        (the segments then hold the bytes as received: look at the status
+        before the bytes) or the message does not fit (none of its segments'
+        bytes is written).  `data` is never written.  status / mismatches:
+        None allocates, False leaves that output out, a tensor is reused (the
+        count is added to).  Fails closed as verify: a call that could not
+        scan its tables writes nothing, flags every message and adds nobj."""
+        mo = self._messages(data, msg_offsets, msg_offsets_host, payload_offset)
+        status, mism = _verdict_buffers(self.nobj, self.device, status, mismatches)
+        work = self._msg_work()
+        base, n = self.meta.data_ptr(), self.nseg
+        self._run("mchecksum_gpu_unpack_segment_messages", stream,
+                  lambda h: _lib().mchecksum_gpu_unpack_segment_messages(b"crc32c", data.data_ptr(), mo.data_ptr(),
+                                                                         self.nobj, payload_offset, hash_offset, base,
+                                                                         base + 8 * n, n, base + 16 * n,
+                                                                         work.data_ptr(), work.numel() * 8,
+                                                                         _ptr(status), _ptr(mism), h))
+        self._starts = mo
+        return status, mism
+
 
 def _check_segment_tables(flat_bytes: int, flat_addr: int, starts, seg_addr, seg_lens, first) -> None:
     """Host check of a gather / scatter call (ValueError), callable without a
@@ -943,6 +1049,24 @@ def scatter_segments(method: str, src: torch.Tensor, src_starts, segments, obj_f
     out = b.scatter(method, src, src_starts, out, stream)
     _after_one_shot(b, stream)
     return out
+
+
+def pack_segment_messages(segments, obj_first, data: torch.Tensor, msg_offsets, payload_offset: int = 20,
+                          hash_offset: int = 16, status=None, stream=None) -> torch.Tensor:
+    """One-shot SegmentBatch(segments, obj_first).pack_messages(data, msg_offsets, ...)."""
+    b = SegmentBatch(segments, obj_first)
+    status = b.pack_messages(data, msg_offsets, payload_offset, hash_offset, status, stream)
+    _after_one_shot(b, stream)
+    return status
+
+
+def unpack_segment_messages(data: torch.Tensor, msg_offsets, segments, obj_first, payload_offset: int = 20,
+                            hash_offset: int = 16, status=None, mismatches=None, stream=None):
+    """One-shot SegmentBatch(segments, obj_first).unpack_messages(data, msg_offsets, ...)."""
+    b = SegmentBatch(segments, obj_first)
+    verdict = b.unpack_messages(data, msg_offsets, payload_offset, hash_offset, status, mismatches, stream)
+    _after_one_shot(b, stream)
+    return verdict
 
 
 def checksum_segments(method: str, segments, obj_first=None, out: torch.Tensor | None = None,
