@@ -6,7 +6,9 @@ Every image is built on the host: the expected message buffer of a pack (a
 guard pattern in the headers, around and between what may be written, 64 bytes
 either side) and the expected segment arena of an unpack (guards between and
 around the segments), compared byte for byte; the hash is the oracle's CRC-32C
-over the concatenated fields, big-endian in the header slot."""
+over the concatenated fields, big-endian in the header slot.  The two tests at
+the non-temporal threshold (512 MiB) build and compare their images on the
+device and take only the hashes from the host."""
 import ctypes
 import os
 
@@ -411,3 +413,124 @@ def test_null_status_and_mismatches(gpu, crc):
     c = _misfit_case(rng)
     check_pack(gpu, c, rng, crc, status=False)
     check_unpack(gpu, c, rng, crc, status=False, mismatches=False)
+
+
+# 10 --------------------------------------------- the non-temporal threshold --
+# seg_msg_copy_kernel takes the non-temporal loads when the scan's total is
+# kSegNtBytes = 512 MiB or more -- every segment counts, those of a message
+# that does not fit too.  One list for both directions, 4099 bytes over: a
+# segment of a chunk + 5 bytes (at an odd address in both tests), an empty
+# segment, a message with no segments, and between fitting messages one whose
+# slot is a byte too long -- the walk steps over its 64 MiB of chunks.
+NT_BYTES = 512 << 20
+M = 1 << 20
+NT_PAY, NT_HOFF = 20, 16
+NT_DELTA = [0, 0, 1, 0, 0]
+# where segment s starts, mod 16: the source offset of a pack, the arena residue of an unpack
+NT_RES = [1, 7, 0, 3, 0, 0, 9, 0, 0, 5, 11, 2]
+
+
+def _nt_list():
+    """(segment lengths, first, message table, bytes per message)."""
+    objs = [[K + 5, 0, 60 * M], [], [40 * M + 3, 24 * M], [64 * M, 64 * M + 1, 64 * M], [64 * M, 17, 64 * M + 7, 0]]
+    objs[4][3] = NT_BYTES + 4099 - sum(sum(o) for o in objs)
+    lens = [n for o in objs for n in o]
+    first = np.concatenate([[0], np.cumsum([len(o) for o in objs])]).astype(np.int64)
+    N = [sum(o) for o in objs]
+    off = (65 + np.concatenate([[0], np.cumsum([NT_PAY + n + d for n, d in zip(N, NT_DELTA)])])).astype(np.int64)
+    assert sum(lens) == NT_BYTES + 4099 and len(lens) == len(NT_RES) and lens[0] == K + 5 and min(lens[2:]) > 0
+    return lens, first, off, N
+
+
+def _enough_memory(nbytes):
+    import torch
+    if torch.cuda.mem_get_info()[0] < nbytes:
+        pytest.skip(f"not enough free device memory for the 512 MiB list ({nbytes >> 20} MiB wanted)")
+
+
+def _same_on_device(got, exp, what):
+    import torch
+    if not torch.equal(got, exp):
+        bad = torch.nonzero(got != exp).flatten()
+        raise AssertionError(f"{what}: {bad.numel()} bytes differ, first at {bad[:5].tolist()}")
+
+
+def _be32(v):
+    import torch
+    return torch.tensor(list(int(v).to_bytes(4, "big")), dtype=torch.uint8, device="cuda")
+
+
+def test_pack_at_the_non_temporal_threshold(gpu, oracle_mod):
+    """The segments are views into one 68 MiB source (reads may alias).  The
+    expected buffer is built on the device -- torch.cat of the same views into
+    a guard-filled buffer -- with the oracle's CRC-32C of each message's
+    fields, computed over a host copy of the source; the whole buffer is
+    compared, guards and the misfit's slot included."""
+    import torch
+    lens, first, off, N = _nt_list()
+    size = int(off[-1]) + 64
+    _enough_memory(4 * size)  # the buffer, the expected one, the compare's temporaries
+    src = torch.empty(max(lens) + 4096, dtype=torch.uint8, device="cuda")
+    gpu.fill_splitmix(src, 0x5E65)
+    host = src.cpu().numpy()
+    assert src.data_ptr() % 16 == 0
+    views = [src[r:r + n] for r, n in zip(NT_RES, lens)]
+    buf = torch.full((size,), GUARD, dtype=torch.uint8, device="cuda")
+    status = gpu.SegmentBatch(views, first).pack_messages(buf, off, NT_PAY, NT_HOFF)
+    torch.cuda.synchronize()
+    exp = torch.full((size,), GUARD, dtype=torch.uint8, device="cuda")
+    for j in range(len(N)):
+        if NT_DELTA[j]:
+            continue
+        m0, segs = int(off[j]), range(first[j], first[j + 1])
+        if N[j]:
+            exp[m0 + NT_PAY:m0 + NT_PAY + N[j]] = torch.cat([views[s] for s in segs])
+        fields = np.concatenate([host[NT_RES[s]:NT_RES[s] + lens[s]] for s in segs] + [np.zeros(0, dtype=np.uint8)])
+        exp[m0 + NT_HOFF:m0 + NT_HOFF + 4] = _be32(oracle_mod.crc("crc32c", fields, "sse42"))
+    _same_on_device(buf, exp, "message buffer")
+    assert status.tolist() == NT_DELTA
+    assert np.array_equal(src.cpu().numpy(), host), "segment memory was written"
+
+
+def test_unpack_at_the_non_temporal_threshold(gpu, oracle_mod):
+    """The message buffer is generated on the device; the hashes come from
+    the oracle over a host copy (batch_offsets over the table header, payload,
+    header, ...: 8 threads).  The segments are distinct slices of one
+    sentinel-filled arena, which is compared on the device with slices of the
+    message buffer: the misfit's segments and every gap keep their sentinels.
+    One fitting message is corrupted after its hash was stored."""
+    import torch
+    lens, first, off, N = _nt_list()
+    size = int(off[-1]) + 64
+    _enough_memory(6 * size)  # buffer and its copy, arena and the expected one, the compare's temporaries
+    buf = torch.empty(size, dtype=torch.uint8, device="cuda")
+    gpu.fill_splitmix(buf, 0x5E66)
+    table = np.stack([off[:-1], off[:-1] + NT_PAY], axis=1).ravel().tolist() + [int(off[-1])]
+    crcs = oracle_mod.batch_offsets("crc32c", buf.cpu().numpy(), np.asarray(table), variant="sse42", nthreads=8)[1::2]
+    assert int(crcs[1]) == oracle_mod.crc("crc32c", b"")  # (the message with no segments: exactly its headers)
+    for j in range(len(N)):
+        if not NT_DELTA[j]:
+            buf[int(off[j]) + NT_HOFF:int(off[j]) + NT_HOFF + 4] = _be32(crcs[j])
+    buf[int(off[3]) + NT_PAY + 100 * M + 3] ^= 0x10  # in message 3's second segment
+    before = buf.clone()
+    at, pos = [], 64
+    for r, n in zip(NT_RES, lens):
+        pos = (pos + 15) // 16 * 16 + r
+        at.append(pos)
+        pos += n + 14
+    assert at[0] % 2 == 1
+    arena = torch.full((pos + 64,), SENT, dtype=torch.uint8, device="cuda")
+    status, mism = gpu.SegmentBatch([arena[a:a + n] for a, n in zip(at, lens)], first).unpack_messages(
+        buf, off, NT_PAY, NT_HOFF)
+    torch.cuda.synchronize()
+    exp = torch.full((pos + 64,), SENT, dtype=torch.uint8, device="cuda")
+    for j in range(len(N)):
+        if NT_DELTA[j]:
+            continue
+        p = int(off[j]) + NT_PAY
+        for s in range(first[j], first[j + 1]):
+            exp[at[s]:at[s] + lens[s]] = buf[p:p + lens[s]]
+            p += lens[s]
+    _same_on_device(arena, exp, "segment arena")
+    _same_on_device(buf, before, "message buffer")
+    assert status.tolist() == [0, 0, 1, 1, 0] and int(mism.item()) == 2

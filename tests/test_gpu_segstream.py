@@ -325,6 +325,90 @@ def test_state_verify(gpu, pool, want, method):
     assert torch.equal(state, before), "state_verify modified the states"
 
 
+# ----------------------------------------------- the non-temporal threshold --
+# A list of kSegNtBytes = 512 MiB and more takes the non-temporal loads in
+# seg_pass (decided on the device from the scan's total): 640 segments of 1 MiB,
+# views that reuse the small pool at 16-B aligned offsets, 4 per object, three
+# of them ragged (an odd start, a length that is no multiple of 1 KiB, a short
+# one).  The oracle hashes a fixed sample of the 160 objects -- the first, the
+# last and the three that hold a ragged segment; all 160 are compared with the
+# same segments run as two lists of 320 MiB, which take the default loads.
+MIB = 1 << 20
+NT_NOBJ = 160
+NT_SAMPLE = (0, 1, 80, 159, 17)
+
+
+@pytest.fixture(scope="module")
+def nt_list(pool):
+    """(segments as (offset, length), first, per object a small segment of an earlier stage)."""
+    _, dev, _ = pool
+    assert dev.data_ptr() % 16 == 0
+    rng = np.random.default_rng(93)
+    segs = [(16 * int(rng.integers(0, (dev.numel() - 64 - MIB) // 16)), MIB) for _ in range(4 * NT_NOBJ)]
+    segs[5] = (segs[5][0] + 3, MIB - 7)
+    segs[322] = (segs[322][0] + 1, MIB - 1029)
+    segs[639] = (segs[639][0] + 7, 5)
+    assert sum(n for _, n in segs) >= 512 * MIB
+    first = list(range(0, 4 * NT_NOBJ + 1, 4))
+    small = [(1 + 37 * j, 3 + 11 * j) for j in range(NT_NOBJ)]  # 3 .. 1752 bytes at odd and even addresses
+    return segs, first, small
+
+
+def _views(dev, segs):
+    return [dev[o:o + n] for o, n in segs]
+
+
+def _in_two_lists(gpu, method, dev, segs, state):
+    """Advance `state` over the objects of the 640-segment list as two calls
+    of 320 MiB each: objects 0..79, then 80..159, the others without segments."""
+    half = 2 * NT_NOBJ
+    quarter = list(range(0, half + 1, 4))
+    gpu.SegmentBatch(_views(dev, segs[:half]), quarter + [half] * (NT_NOBJ // 2)).update(method, state)
+    gpu.SegmentBatch(_views(dev, segs[half:]), [0] * (NT_NOBJ // 2) + quarter).update(method, state)
+    return state
+
+
+def _sample_bytes(host, segs, first, j):
+    return [host[o:o + n] for o, n in segs[first[j]:first[j + 1]]]
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_update_segments_at_the_non_temporal_threshold(gpu, pool, nt_list, oracle_mod, method):
+    """The states come from a small stage, so the chunk pass's XORs land on
+    seeded states (seg_pre_kernel<T, true>)."""
+    import torch
+    _, dev, host = pool
+    segs, first, small = nt_list
+    state = gpu.state_init(method, NT_NOBJ)
+    gpu.SegmentBatch(_views(dev, small), list(range(NT_NOBJ + 1))).update(method, state)
+    ref = _in_two_lists(gpu, method, dev, segs, state.clone())
+    gpu.SegmentBatch(_views(dev, segs), first).update(method, state)
+    got = _vals(gpu, method, state)
+    for j in NT_SAMPLE:
+        parts = [host[small[j][0]:small[j][0] + small[j][1]]] + _sample_bytes(host, segs, first, j)
+        assert got[j] == oracle_mod.crc(method, np.concatenate(parts)), j
+    assert torch.equal(state, ref), "the states differ from the same objects' in two lists under the threshold"
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_verify_segments_at_the_non_temporal_threshold(gpu, pool, nt_list, oracle_mod, method):
+    import torch
+    _, dev, host = pool
+    segs, first, _ = nt_list
+    good = _vals(gpu, method, _in_two_lists(gpu, method, dev, segs, gpu.state_init(method, NT_NOBJ)))
+    for j in NT_SAMPLE:
+        assert good[j] == oracle_mod.crc(method, np.concatenate(_sample_bytes(host, segs, first, j))), j
+    planted = list(good)
+    planted[17] ^= 1        # one of the sample, so a value the oracle gave
+    planted[101] ^= 1 << 31
+    b = gpu.SegmentBatch(_views(dev, segs), first)
+    mism = torch.full((1,), 5, dtype=torch.int32, device="cuda")
+    status, mism = b.verify(method, _signed(gpu, method, planted), mismatches=mism)
+    assert np.nonzero(status.cpu().numpy())[0].tolist() == [17, 101] and int(mism.item()) == 7
+    status, mism = b.verify(method, _signed(gpu, method, good))
+    assert int(status.sum().item()) == 0 and int(mism.item()) == 0
+
+
 # -------------------------------------------------------------- fail closed --
 # tests/test_gpu_fail_closed.py's bound: a call whose waits are never satisfied
 # returns within about one deadline (1 s)

@@ -19,14 +19,44 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QLIB = os.path.join(ROOT, "build", "libmchecksum_qfault.so")
 
-# both kernel layouts: "0" the latency layout, "1" the throughput layout
-LAYOUTS = ["0", "1"]
+# the kernels a call can take: "0" the latency layout, "1" the throughput layout
+# with default loads, "1-nt" the same with non-temporal loads (MCHECKSUM_GPU_NT=1:
+# what a batch of 8192 messages and more takes by itself; the latency layout
+# has no such variant)
+LAYOUTS = ["0", "1", "1-nt"]
 HASH = 16
-# the edges of the 4-byte pad, the 64 lane ranges and kXdrFastMin = 256
-LENS = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1000]
+# The throughput layout's step loop (payload32_g64: fields of kXdrFastMin = 256
+# bytes and more) moves 1024 bytes a step through a ring of kRingOff = 8 steps:
+# one step, two steps, the ring's fill (8 KiB) and two rings (16 KiB: the first
+# length whose steady loop, which loads a step as it folds one, runs at all),
+# each with its neighbours.  The start alignment shifts the step count by one.
+RING_LENS = [1023, 1024, 1025, 2047, 2048, 2049, 8191, 8192, 8193, 16383, 16384, 16385]
+# the edges of the 4-byte pad, the 64 lane ranges and kXdrFastMin = 256; then the ring's
+LENS = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1000] + RING_LENS
 BIG = 70001
 NMSG = 300
+# messages RING_AT + 2k and RING_AT + 2k + 1 carry RING_LENS[k] whatever the draw: an
+# odd and an even message start each, so an odd source and an odd destination address
+RING_AT = 104
 SENTINEL = 0xA5
+
+
+def _path(monkeypatch, layout):
+    """Select the kernel of LAYOUTS' entry `layout` (the library re-reads its
+    settings on every change made through this monkeypatch)."""
+    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout[0])
+    if layout.endswith("-nt"):
+        monkeypatch.setenv("MCHECKSUM_GPU_NT", "1")
+    else:
+        monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
+
+
+def _forced_len(i):
+    """The length message i of a NMSG batch carries whatever the draw, or None."""
+    if i % 97 == 5:
+        return BIG
+    k = (i - RING_AT) // 2
+    return RING_LENS[k] if 0 <= k < len(RING_LENS) else None
 
 
 def _schemas(O):
@@ -40,9 +70,9 @@ def _schemas(O):
     }
 
 
-def _values(rng, schema, O, big):
+def _values(rng, schema, O, force):
     """Random field values; an INT that a length-driven field or a SKIP reads
-    is drawn from LENS (`big`: the first such INT is BIG)."""
+    is drawn from LENS (`force`, unless None: the first such INT is that)."""
     vals, last, f = [], None, 0
     while f < len(schema):
         kind, size = schema[f]
@@ -54,8 +84,8 @@ def _values(rng, schema, O, big):
         nxt = schema[f + 1][0] if f + 1 < len(schema) else None
         if kind == O.XDR_INT:
             if nxt in (O.XDR_OPAQUE_LEN, O.XDR_RAW_LEN, O.XDR_SKIP_IF_ZERO):
-                v = BIG if big else int(rng.choice(LENS))
-                big = False
+                v = force if force is not None else int(rng.choice(LENS))
+                force = None
             else:
                 v = int(rng.integers(-(1 << (8 * size - 1)), 1 << (8 * size - 1)))
             vals.append(v)
@@ -70,12 +100,12 @@ def _values(rng, schema, O, big):
 class Batch:
     """Messages (hash slots zero) whose starts fall on every residue mod 16."""
 
-    def __init__(self, O, kind, pay, seed, count=NMSG):
+    def __init__(self, O, kind, pay, seed, count=NMSG, forced=_forced_len):
         self.kind, self.pay, self.schema = kind, pay, _schemas(O)[kind]
         rng = np.random.default_rng(seed)
         self.msgs, self.xdr_len, pos = [], [], 0
         for i in range(count):
-            xdr = O.xdr_encode(self.schema, _values(rng, self.schema, O, i % 97 == 5))
+            xdr = O.xdr_encode(self.schema, _values(rng, self.schema, O, forced(i)))
             hdr = bytearray(rng.integers(0, 256, pay, dtype=np.uint8).tobytes())
             hdr[HASH:HASH + 4] = b"\0\0\0\0"
             n = pay + len(xdr)
@@ -83,11 +113,16 @@ class Batch:
             self.msgs.append(bytes(hdr) + xdr + rng.integers(0, 256, slack, dtype=np.uint8).tobytes())
             self.xdr_len.append(len(xdr))
             pos += n + slack
-        self._crc = {}
+        self._crc, self._streams = {}, None
+
+    def streams(self, O):
+        if self._streams is None:
+            self._streams = [O.xdr_hashed_stream(self.schema, m[self.pay:]) for m in self.msgs]
+        return self._streams
 
     def crcs(self, O, method):
         if method not in self._crc:
-            self._crc[method] = [O.crc(method, O.xdr_hashed_stream(self.schema, m[self.pay:])) for m in self.msgs]
+            self._crc[method] = [O.crc(method, s) for s in self.streams(O)]
         return self._crc[method]
 
     def sealed(self, O, method):
@@ -147,11 +182,13 @@ CASES = [("iovec", 20), ("mixed", 23), ("iovec", 23), ("mixed", 20)]
 @pytest.mark.parametrize("kind,pay", CASES)
 def test_seal_then_verify_round_trip(gpu, oracle_mod, kind, pay, method, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     assert {int(o) % 16 for o in _table(b.msgs)[:-1]} == set(range(16))
     data, offs, off, blob = _upload(b.msgs)
+    if kind == "iovec":  # the body lies behind the headers and the u32 length: every ring length at an odd address
+        assert {b.xdr_len[i] - 4 for i in range(NMSG) if (off[i] + pay + 4) % 2} >= {n + -n % 4 for n in RING_LENS}
     st = gpu.seal_xdr_messages(method, data, offs, b.schema, payload_offset=pay, offsets_host=off)
     torch.cuda.synchronize()
     assert int(st.sum().item()) == 0
@@ -213,7 +250,7 @@ def _damaged(O, b, method):
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_verify_flags_exactly_the_failures(gpu, oracle_mod, kind, pay, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, method = oracle_mod, "crc32c"
     b = _batch(O, kind, pay)
     msgs, idx = _damaged(O, b, method)
@@ -287,11 +324,15 @@ def _unpack_case(O, b, method):
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_unpack_decodes_and_verifies(gpu, oracle_mod, kind, pay, method, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     msgs, doff, want_st, want, idx = _unpack_case(O, b, method)
     data, offs, off, blob = _upload(msgs)
+    if kind == "iovec":  # every ring length is read at an odd address, and stored at one (entry 2i is message i)
+        body = {i: int(doff[2 * i + 1] - doff[2 * i]) - 4 for i in range(RING_AT, NMSG)}
+        assert {n for i, n in body.items() if (off[2 * i] + pay + 4) % 2} >= set(RING_LENS)
+        assert {n for i, n in body.items() if (doff[2 * i] + 4) % 2} >= set(RING_LENS)
     dst = torch.full((want.size,), SENTINEL, dtype=torch.uint8, device="cuda")
     st, mism = gpu.unpack_xdr_messages(method, data, offs, b.schema, dst, torch.from_numpy(doff).cuda(),
                                        payload_offset=pay, offsets_host=off, dst_offsets_host=doff)
@@ -307,12 +348,134 @@ def test_unpack_decodes_and_verifies(gpu, oracle_mod, kind, pay, method, layout,
     assert np.array_equal(data.cpu().numpy()[:blob.size], blob), "unpack wrote to the source"
 
 
+# ------------------------------------------------- the default count rule ----
+# With no setting, a batch takes the throughput layout past 1024 messages and
+# its non-temporal kernel from 8192 on (launch_plan.h: nt_by_count): 8192 is the
+# smallest count that runs xdr_msg_fast_kernel<OP, true> by itself, 8191 the
+# largest that runs <OP, false>.
+
+RULE_COUNTS = [8191, 8192]
+RULE_BIG_AT = 4100
+RULE_LARGE = [n for n in LENS if n >= 256]
+
+
+def _rule_len(i):
+    """iovec lengths under 64; about every 64th message (every 63rd: coprime
+    to the 16 start residues) carries the next of LENS' lengths from 256 up,
+    and one carries BIG."""
+    if i == RULE_BIG_AT:
+        return BIG
+    if i % 63 == 9:
+        return RULE_LARGE[(i // 63) % len(RULE_LARGE)]
+    return (37 * i + 11) % 64
+
+
+def _rule_batch(O):
+    if "rule" not in _batches:
+        _batches["rule"] = Batch(O, "iovec", 20, 4242, count=RULE_COUNTS[-1], forced=_rule_len)
+    return _batches["rule"]
+
+
+def _no_settings(monkeypatch):
+    monkeypatch.delenv("MCHECKSUM_GPU_XDR_FAST", raising=False)
+    monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
+
+
+def _rule_damage(O, b, method, count):
+    """The first `count` sealed messages with a body byte flipped in BIG and in
+    a 16 KiB body, a hash byte flipped in a tiny message and the last message
+    cut by a byte; the oracle's verdict for each: (messages, bad)."""
+    msgs, pay = b.sealed(O, method)[:count], b.pay
+    big16 = next(i for i in range(count) if b.xdr_len[i] == 4 + 16384)
+    msgs[RULE_BIG_AT] = _flip(msgs[RULE_BIG_AT], pay + 4 + 60001)
+    msgs[big16] = _flip(msgs[big16], pay + 4 + 9000)
+    msgs[77] = _flip(msgs[77], HASH + 1)
+    last = next(i for i in range(count - 1, 0, -1) if b.xdr_len[i] > 4)
+    msgs[last] = msgs[last][:pay + b.xdr_len[last] - 1]
+    bad = np.zeros(count, dtype=np.uint8)  # (sealed with the oracle's CRC: the others verify by construction)
+    for i in (RULE_BIG_AT, big16, 77, last):
+        bad[i] = _verdicts(O, method, b.schema, pay, [msgs[i]])[0][0]
+    assert bad.sum() == 4
+    return msgs, bad
+
+
+@pytest.mark.parametrize("count", RULE_COUNTS)
+def test_seal_by_the_default_count_rule(gpu, oracle_mod, count, monkeypatch):
+    import torch
+    _no_settings(monkeypatch)
+    O, method = oracle_mod, "crc32c"
+    b = _rule_batch(O)
+    assert {int(o) % 16 for o in _table(b.msgs)[:-1]} == set(range(16))
+    data, offs, off, blob = _upload(b.msgs[:count])
+    st = gpu.seal_xdr_messages(method, data, offs, b.schema, payload_offset=b.pay, offsets_host=off)
+    torch.cuda.synchronize()
+    assert int(st.sum().item()) == 0
+    got = data.cpu().numpy()
+    want = np.frombuffer(b"".join(b.sealed(O, method)[:count]), dtype=np.uint8)
+    bad = np.nonzero(got[:blob.size] != want)[0]
+    assert bad.size == 0, f"{bad.size} bytes differ from the oracle's sealed messages, first at {bad[:5]}"
+    assert not got[blob.size:].any()
+
+
+@pytest.mark.parametrize("count", RULE_COUNTS)
+def test_verify_by_the_default_count_rule(gpu, oracle_mod, count, monkeypatch):
+    import torch
+    _no_settings(monkeypatch)
+    O, method = oracle_mod, "crc32c"
+    b = _rule_batch(O)
+    msgs, want = _rule_damage(O, b, method, count)
+    data, offs, off, blob = _upload(msgs)
+    st, mism = gpu.verify_xdr_messages(method, data, offs, b.schema, payload_offset=b.pay, offsets_host=off)
+    torch.cuda.synchronize()
+    assert np.array_equal(st.cpu().numpy(), want)
+    assert int(mism.item()) == int(want.sum())
+    assert np.array_equal(data.cpu().numpy()[:blob.size], blob), "verify wrote to the buffer"
+
+
+@pytest.mark.parametrize("count", RULE_COUNTS)
+def test_unpack_by_the_default_count_rule(gpu, oracle_mod, count, monkeypatch):
+    """Every slot is as long as its message's hashed stream, but one (a 8 KiB
+    body's, a byte longer: not written); slots start 37 bytes in and follow
+    one another, so their starts fall on every residue mod 16."""
+    import torch
+    _no_settings(monkeypatch)
+    O, method = oracle_mod, "crc32c"
+    b = _rule_batch(O)
+    msgs, bad = _rule_damage(O, b, method, count)
+    verd = [(0, s) for s in b.streams(O)[:count]]
+    for i in np.nonzero(bad)[0]:
+        verd[i] = _verdicts(O, method, b.schema, b.pay, [msgs[i]])[0]
+    misfit = next(i for i in range(count) if b.xdr_len[i] == 4 + 8192)
+    slots = [len(s) if s is not None else 10 for _, s in verd]
+    slots[misfit] += 1
+    doff = np.concatenate([[37], 37 + np.cumsum(slots)]).astype(np.int64)
+    assert {int(d) % 16 for d in doff[:-1]} == set(range(16))
+    want = np.full(int(doff[-1]) + 29, SENTINEL, dtype=np.uint8)
+    want_st = np.ones(count, dtype=np.uint8)
+    for i, (fails, s) in enumerate(verd):
+        if s is not None and i != misfit:
+            want[doff[i]:doff[i + 1]] = np.frombuffer(s, dtype=np.uint8)
+            want_st[i] = fails
+    assert want_st.sum() == 5
+    data, offs, off, blob = _upload(msgs)
+    dst = torch.full((want.size,), SENTINEL, dtype=torch.uint8, device="cuda")
+    st, mism = gpu.unpack_xdr_messages(method, data, offs, b.schema, dst, torch.from_numpy(doff).cuda(),
+                                       payload_offset=b.pay, offsets_host=off, dst_offsets_host=doff)
+    torch.cuda.synchronize()
+    got = dst.cpu().numpy()
+    wrong = np.nonzero(got != want)[0]
+    assert wrong.size == 0, f"{wrong.size} destination bytes differ, first at {wrong[:5]}"
+    assert np.array_equal(st.cpu().numpy(), want_st)
+    assert int(mism.item()) == int(want_st.sum())
+    assert np.array_equal(data.cpu().numpy()[:blob.size], blob), "unpack wrote to the source"
+
+
 # --------------------------------------------- empty batch, empty schema ----
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_empty_batch_and_empty_schema(gpu, oracle_mod, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     schema = _schemas(O)["iovec"]
     data = torch.zeros(64, dtype=torch.uint8, device="cuda")
@@ -353,7 +516,7 @@ def test_graph_replay_reads_current_contents(gpu, oracle_mod, layout, monkeypatc
     """verify and unpack captured after prepare(): a replay judges the bytes
     and the tables as they are at that moment."""
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, method, pay = oracle_mod, "crc32c", 20
     gpu.prepare(method)
     b = _batch(O, "iovec", pay)
@@ -432,7 +595,7 @@ def test_graph_replay_reads_current_contents(gpu, oracle_mod, layout, monkeypatc
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_checksum_xdr_values_after_the_message_calls(gpu, oracle_mod, kind, pay, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     data, offs, off, blob = _upload(b.msgs)

@@ -31,14 +31,44 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QLIB = os.path.join(ROOT, "build", "libmchecksum_qfault.so")
 
-# both kernel layouts: "0" the latency layout, "1" the throughput layout
-LAYOUTS = ["0", "1"]
+# the kernels a call can take: "0" the latency layout, "1" the throughput layout
+# with default loads, "1-nt" the same with non-temporal loads (MCHECKSUM_GPU_NT=1:
+# what a batch of 8192 messages and more takes by itself; the latency layout
+# has no such variant)
+LAYOUTS = ["0", "1", "1-nt"]
 HASH = 16
-# the edges of the 4-byte pad, the 64 lane ranges and kXdrFastMin = 256
-LENS = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1000]
+# The throughput layout's copying step loop (payload32_g64: fields of kXdrFastMin
+# = 256 bytes and more) moves 1024 bytes a step through a ring of kRingOff = 8
+# steps: one step, two steps, the ring's fill (8 KiB) and two rings (16 KiB: the
+# first length whose steady loop, which loads a step as it folds one, runs at
+# all), each with its neighbours.  The start alignment shifts the step count by one.
+RING_LENS = [1023, 1024, 1025, 2047, 2048, 2049, 8191, 8192, 8193, 16383, 16384, 16385]
+# the edges of the 4-byte pad, the 64 lane ranges and kXdrFastMin = 256; then the ring's
+LENS = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1000] + RING_LENS
 BIG = 70001
 NMSG = 300
+# messages RING_AT + 2k and RING_AT + 2k + 1 carry RING_LENS[k] whatever the draw: an
+# odd and an even image start each, over message starts of both parities (Batch)
+RING_AT = 104
 SENTINEL = 0xA5
+
+
+def _path(monkeypatch, layout):
+    """Select the kernel of LAYOUTS' entry `layout` (the library re-reads its
+    settings on every change made through this monkeypatch)."""
+    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout[0])
+    if layout.endswith("-nt"):
+        monkeypatch.setenv("MCHECKSUM_GPU_NT", "1")
+    else:
+        monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
+
+
+def _forced_len(i):
+    """The length message i of a NMSG batch carries whatever the draw, or None."""
+    if i % 97 == 5:
+        return BIG
+    k = (i - RING_AT) // 2
+    return RING_LENS[k] if 0 <= k < len(RING_LENS) else None
 I, OP, OPL, RAW, RAWL, SKIP, S = 0, 1, 2, 3, 4, 5, 6  # MCHECKSUM_XDR_*; S = MCHECKSUM_XDR_SINT
 
 SCHEMAS = {
@@ -55,9 +85,9 @@ def _osch(schema):
     return [(I if k == S else k, z) for k, z in schema]
 
 
-def _values(rng, schema, big):
+def _values(rng, schema, force):
     """Random field values; an integer that a length-driven field or a SKIP
-    reads is drawn from LENS (`big`: the first such is BIG).  INT values are
+    reads is drawn from LENS (`force`, unless None: the first such is that).  INT values are
     non-negative over the whole unsigned range, SINT values over the signed."""
     vals, last, f = [], None, 0
     while f < len(schema):
@@ -70,8 +100,8 @@ def _values(rng, schema, big):
         nxt = schema[f + 1][0] if f + 1 < len(schema) else None
         if kind in (I, S):
             if nxt in (OPL, RAWL, SKIP):
-                v = BIG if big else int(rng.choice(LENS))
-                big = False
+                v = force if force is not None else int(rng.choice(LENS))
+                force = None
             elif kind == S:
                 v = int(rng.integers(-(1 << (8 * size - 1)), 1 << (8 * size - 1), dtype=np.int64))
             else:
@@ -146,11 +176,11 @@ class Batch:
     is message i, entry 2i + 1 a gap sized so that image i starts on residue
     i mod 16 and message i on residue (i // 16) mod 16."""
 
-    def __init__(self, O, kind, pay, seed, count=NMSG):
+    def __init__(self, O, kind, pay, seed, count=NMSG, forced=_forced_len):
         self.kind, self.pay, self.schema = kind, pay, SCHEMAS[kind]
         self.rng = rng = np.random.default_rng(seed)
         osch = _osch(self.schema)
-        self.values = [_values(rng, self.schema, i % 97 == 5) for i in range(count)]
+        self.values = [_values(rng, self.schema, forced(i)) for i in range(count)]
         self.wires = [O.xdr_encode(osch, v) for v in self.values]
         self.images = [O.xdr_hashed_stream(osch, w) for w in self.wires]
         self.parts, self.slots, spos, mpos = [], [], 0, 0
@@ -226,7 +256,7 @@ def test_sign_and_zero_extension_by_hand(gpu, oracle_mod):
              + (-2 & (2**64 - 1)).to_bytes(8, "little") + bytes([0x7F]))
     wire = bytes.fromhex("00000080 ffffff80 00008000 fffffffe 80000000 ffffffff fffffffffffffffe 0000007f")
     assert wire == oracle_mod.xdr_encode(_osch(schema), [0x80, -128, 0x8000, -2, 0x80000000, -1, -2, 0x7F])
-    for layout in LAYOUTS:
+    for layout in ("0", "1"):  # (integers only: no field reaches the step loop, whose loads MCHECKSUM_GPU_NT picks)
         os.environ["MCHECKSUM_GPU_XDR_FAST"] = layout
         try:
             gpu._lib().mchecksum_gpu_reload_settings()
@@ -247,13 +277,19 @@ def test_sign_and_zero_extension_by_hand(gpu, oracle_mod):
 @pytest.mark.parametrize("method", ["crc32c", "crc32"])
 @pytest.mark.parametrize("kind,pay", CASES)
 def test_pack_writes_exactly_the_wire_and_the_hash(gpu, oracle_mod, kind, pay, method, layout, monkeypatch):
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     soff, moff = b.tables()
     if kind == "iovec":
         assert {(int(s) % 16, int(m) % 16) for s, m in zip(soff[0:-1:2], moff[0:-1:2])} == {
             (s, m) for s in range(16) for m in range(16)}
+        # the body lies behind the u32 length on both sides: every ring length is read at an odd address
+        # and, in one of the two iovec cases (the message starts of a parity differ by payload_offset),
+        # stored at one
+        odd = [{len(b.images[i]) - 4 for i in range(RING_AT, NMSG) if (soff[2 * i] + 4) % 2 and (moff[2 * i] + pay + 4) % 2 == p}
+               for p in (0, 1)]
+        assert odd[0] | odd[1] >= set(RING_LENS) and odd[0] and odd[1]
     else:
         # both extensions occur for every size below 8
         ints = [[v for (k, z), v in zip([e for e in b.schema if e[0] != SKIP], vals)] for vals in b.values]
@@ -263,13 +299,60 @@ def test_pack_writes_exactly_the_wire_and_the_hash(gpu, oracle_mod, kind, pay, m
     assert not st[0::2].any() and st[1::2].all()  # every message packed, every gap entry refused
 
 
+# ------------------------------------------------- the default count rule ----
+# With no setting, a batch takes the throughput layout past 1024 messages and
+# its non-temporal kernel from 8192 on (launch_plan.h: nt_by_count): 8192 is the
+# smallest count that runs xdr_pack_fast_kernel<true> by itself, 8191 the
+# largest that runs <false>.
+
+RULE_COUNTS = [8191, 8192]
+RULE_BIG_AT = 4100
+RULE_LARGE = [n for n in LENS if n >= 256]
+
+
+def _rule_len(i):
+    """iovec lengths under 64; about every 64th message (every 63rd: coprime
+    to the 16 start residues) carries the next of LENS' lengths from 256 up,
+    and one carries BIG."""
+    if i == RULE_BIG_AT:
+        return BIG
+    if i % 63 == 9:
+        return RULE_LARGE[(i // 63) % len(RULE_LARGE)]
+    return (37 * i + 11) % 64
+
+
+@pytest.mark.parametrize("count", RULE_COUNTS)
+def test_pack_by_the_default_count_rule(gpu, oracle_mod, count, monkeypatch):
+    """Messages alone, no gap entries: entry i is message i.  Two do not fit
+    (a 16 KiB body's slot a byte long, a tiny one's image a byte short); every
+    byte of the buffer and every status as the oracle and the tables say."""
+    monkeypatch.delenv("MCHECKSUM_GPU_XDR_FAST", raising=False)
+    monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
+    O = oracle_mod
+    if "rule" not in _batches:
+        # (payload_offset 23: a slot is 27 bytes and a multiple of 4, so the message starts take every residue)
+        _batches["rule"] = Batch(O, "iovec", 23, 4343, count=RULE_COUNTS[-1], forced=_rule_len)
+    b = _batches["rule"]
+    images, slots = list(b.images[:count]), list(b.slots[0:2 * count:2])
+    long16 = next(i for i in range(count) if len(images[i]) == 4 + 16384)
+    slots[long16] += 1
+    assert len(images[78]) > 4
+    images[78] = images[78][:-1]
+    # images from byte 0 on, messages from byte 7 on: both sides' starts fall on every residue mod 16
+    soff, moff = _table([len(x) for x in images]), _table(slots, 7)
+    assert {int(o) % 16 for o in soff[:-1]} == {int(o) % 16 for o in moff[:-1]} == set(range(16))
+    prefill = np.full(int(moff[-1]) + 37, SENTINEL, dtype=np.uint8)
+    _, _, st = _pack_and_check(gpu, O, b.schema, b.pay, "crc32c", b.src(images), soff, prefill, moff)
+    assert np.nonzero(st)[0].tolist() == sorted([78, long16])
+
+
 # ------------------------------------------------------------ round trip ----
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_round_trip_through_verify_and_unpack(gpu, oracle_mod, kind, pay, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, method = oracle_mod, "crc32c"
     b = _batch(O, kind, pay)
     # the messages alone (no gap entries), so that every entry verifies
@@ -330,7 +413,7 @@ def _misfit_case(O, b):
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_misfits_are_exact(gpu, oracle_mod, kind, pay, layout, monkeypatch):
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     src, soff, moff, idx = _misfit_case(O, b)
@@ -382,7 +465,7 @@ def test_tables_from_the_size_calls_fit(gpu, oracle_mod, kind, pay, layout, monk
     """Sender and receiver build their tables on the device (torch.cumsum of the
     size calls' results): every message fits, no host-side length is used."""
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, method = oracle_mod, "crc32"
     b = _batch(O, kind, pay)
     src, soff = b.src(b.images), _table([len(x) for x in b.images])
@@ -413,7 +496,7 @@ def test_tables_from_the_size_calls_fit(gpu, oracle_mod, kind, pay, layout, monk
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_empty_batch_and_empty_schema(gpu, oracle_mod, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, schema = oracle_mod, SCHEMAS["iovec"]
     data = torch.zeros(64, dtype=torch.uint8, device="cuda")
     src = torch.zeros(64, dtype=torch.uint8, device="cuda")
@@ -444,7 +527,7 @@ def test_graph_replay_reads_current_contents(gpu, oracle_mod, layout, monkeypatc
     """Captured after prepare(): a replay packs the source contents and follows
     both tables as they are at that moment."""
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O, method, pay = oracle_mod, "crc32c", 20
     gpu.prepare(method)
     b = _batch(O, "iovec", pay)
@@ -494,7 +577,7 @@ def test_graph_replay_reads_current_contents(gpu, oracle_mod, layout, monkeypatc
 @pytest.mark.parametrize("kind,pay", CASES[:2])
 def test_existing_calls_after_pack_and_with_sint(gpu, oracle_mod, kind, pay, layout, monkeypatch):
     import torch
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     b = _batch(O, kind, pay)
     osch = _osch(b.schema)

@@ -88,44 +88,76 @@ def _run(gpu, method, msgs, schema, status=False):
     return gpu.as_unsigned(r)
 
 
-# both kernel layouts: "0" the latency layout (byte-table walk), "1" the
-# throughput layout (payload step loop for fields >= 256 B, work queue)
-LAYOUTS = ["0", "1"]
+# the kernels a call can take: "0" the latency layout (byte-table walk), "1"
+# the throughput layout (payload step loop for fields >= 256 B, work queue) with
+# default loads, "1-nt" the same with non-temporal loads (MCHECKSUM_GPU_NT=1:
+# what a batch of 8192 messages and more takes by itself; the latency layout
+# has no such variant)
+LAYOUTS = ["0", "1", "1-nt"]
+# every reflected 32- and 64-bit model ("crc64" is crc64-xz).  crc64-jones: zero
+# initial value (the running register the step loop starts from is then 0 at
+# the first field); crc32, crc64-go-iso: a second polynomial of either width
+METHODS = ["crc32c", "crc32", "crc64", "crc64-go-iso", "crc64-jones"]
+
+
+def _path(monkeypatch, layout):
+    """Select the kernel of LAYOUTS' entry `layout` (the library re-reads its
+    settings on every change made through this monkeypatch)."""
+    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout[0])
+    if layout.endswith("-nt"):
+        monkeypatch.setenv("MCHECKSUM_GPU_NT", "1")
+    else:
+        monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("method", ["crc32c", "crc64"])
 def test_gpu_xdr_test_proc_fixtures(gpu, method, layout, monkeypatch):
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     for name, e in GOLD["payloads"].items():
         schema = [tuple(f) for f in e["xdr_schema"]]
         got = _run(gpu, method, [bytes.fromhex(e["xdr_hex"])] * 3, schema)
         assert got.tolist() == [int(e[method], 16)] * 3, name
 
 
+_shared = {}
+
+
+def _once(key, make):
+    """A batch and its oracle values are built once and shared by the cases that use them."""
+    if key not in _shared:
+        _shared[key] = make()
+    return _shared[key]
+
+
+def _oracle_crcs(O, key, method, schema, msgs):
+    return _once((key, method), lambda: [O.crc(method, O.xdr_hashed_stream(schema, m)) for m in msgs])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", LAYOUTS)
-# crc64-jones: zero initial value (the running register the step loop starts
-# from is then 0 at the first field); crc32: a second 32-bit polynomial
-@pytest.mark.parametrize("method", ["crc32c", "crc64", "crc64-jones", "crc32"])
+@pytest.mark.parametrize("method", METHODS)
 @pytest.mark.parametrize("kind", ["iovec", "mixed"])
 def test_gpu_xdr_random_messages(gpu, oracle_mod, method, kind, layout, monkeypatch):
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     schema = _schemas(O)[kind]
-    rng = np.random.default_rng(17 if kind == "iovec" else 18)
-    msgs = [O.xdr_encode(schema, _random_values(rng, schema, O, 70000 if i % 97 == 0 else 3000))
-            for i in range(700)]
+
+    def make():
+        rng = np.random.default_rng(17 if kind == "iovec" else 18)
+        return [O.xdr_encode(schema, _random_values(rng, schema, O, 70000 if i % 97 == 0 else 3000))
+                for i in range(700)]
+
+    msgs = _once(("random", kind), make)
     got = _run(gpu, method, msgs, schema)
-    want = [O.crc(method, O.xdr_hashed_stream(schema, m)) for m in msgs]
-    assert got.tolist() == want
+    assert got.tolist() == _oracle_crcs(O, ("random", kind), method, schema, msgs)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_gpu_xdr_truncated_messages_are_flagged(gpu, oracle_mod, layout, monkeypatch):
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
+    _path(monkeypatch, layout)
     O = oracle_mod
     schema = _schemas(O)["mixed"]
     rng = np.random.default_rng(5)
@@ -158,6 +190,38 @@ def test_gpu_xdr_large_iovec_batch(gpu, oracle_mod, method):
     assert got.tolist() == want
 
 
+BIG = 70001
+
+
+def _rule_messages(O):
+    """(schema, 8192 iovec messages): lengths under 64; about every 64th (every
+    63rd) carries the next of LENS' lengths from 256 up, and one carries BIG."""
+    schema = _schemas(O)["iovec"]
+    rng = np.random.default_rng(41)
+    large = [n for n in LENS if n >= 256]
+    msgs = []
+    for i in range(8192):
+        n = BIG if i == 4100 else large[(i // 63) % len(large)] if i % 63 == 9 else (37 * i + 11) % 64
+        msgs.append(O.xdr_encode(schema, [n, rng.integers(0, 256, n, dtype=np.uint8).tobytes()]))
+    return schema, msgs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [8191, 8192])
+@pytest.mark.parametrize("method", ["crc32c", "crc64"])
+def test_gpu_xdr_default_count_rule(gpu, oracle_mod, method, count, monkeypatch):
+    """With no setting, a batch takes the throughput layout past 1024 messages
+    and its non-temporal kernel from 8192 on (launch_plan.h: nt_by_count): 8192
+    is the smallest count that runs xdr_fast_kernel<W, true> by itself, 8191 the
+    largest that runs <W, false>.  Every CRC equal to the oracle's."""
+    monkeypatch.delenv("MCHECKSUM_GPU_XDR_FAST", raising=False)
+    monkeypatch.delenv("MCHECKSUM_GPU_NT", raising=False)
+    O = oracle_mod
+    schema, msgs = _once("rule", lambda: _rule_messages(O))
+    got = _run(gpu, method, msgs[:count], schema)
+    assert got.tolist() == _oracle_crcs(O, "rule", method, schema, msgs)[:count]
+
+
 @pytest.mark.gpu
 def test_gpu_xdr_rejects_bad_schemas(gpu):
     import torch
@@ -170,33 +234,49 @@ def test_gpu_xdr_rejects_bad_schemas(gpu):
         gpu.checksum_xdr("crc16", data, offs, [(0, 4)])
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("method", ["crc32c", "crc64", "crc64-jones"])
-def test_gpu_xdr_fast_field_edges(gpu, oracle_mod, method, layout, monkeypatch):
-    """Field lengths around the throughput layout's step-loop threshold
-    (kXdrFastMin = 256: shorter fields take the byte walk, longer ones the
-    1 KiB step loop started from the running register), around the 1 KiB
-    step and the 128-B grid, at every start alignment mod 16 (a raw lead-in
-    of 0..15 bytes), and three large fields in one message (the register runs
-    from one step loop into the next): every CRC equal to the oracle's over
-    the hashed stream."""
-    monkeypatch.setenv("MCHECKSUM_GPU_XDR_FAST", layout)
-    O = oracle_mod
+# Field lengths of the edge tests.  Up to 5: the 4-byte pad; 7..129: the 64
+# lane ranges and the 128-B grid; 252..260: kXdrFastMin = 256, where the step
+# loop takes over; 383, 384, 1151, 1152: the grid inside a step.  The step loop
+# (payload32_g64 / payload64_g64) moves 1024 bytes a step through a ring of
+# kRingOff = 8 (CRC-32) or kRingOff64 = 4 (CRC-64) steps: 1020..1025 and
+# 2047..2049 are one and two steps, 4095..4099 the CRC-64 ring's fill, 8191..8193
+# the CRC-32 ring's fill and two CRC-64 rings (the first length whose steady
+# loop, which loads a step as it folds one, runs at all), 16383..16385 two
+# CRC-32 rings.  The start alignment shifts the step count by one either way.
+LENS = [0, 1, 3, 4, 5, 7, 8, 9, 127, 128, 129, 252, 255, 256, 257, 260, 383, 384, 1020, 1023, 1024, 1025,
+        1151, 1152, 2047, 2048, 2049, 4095, 4096, 4097, 4099, 8191, 8192, 8193, 16383, 16384, 16385]
+
+
+def _edge_messages(O):
+    """(schema, messages): every length of LENS behind a raw lead-in of 0..15 bytes."""
     I, OPL, RAWL, OP = O.XDR_INT, O.XDR_OPAQUE_LEN, O.XDR_RAW_LEN, O.XDR_OPAQUE
     rng = np.random.default_rng(31)
-    lens = [0, 1, 3, 4, 5, 7, 8, 9, 127, 128, 129, 252, 255, 256, 257, 260, 383, 384, 1020, 1023, 1024, 1025,
-            1151, 1152, 2047, 2048, 4099]
     # lead-in length + bytes, the field under test, a fixed 300-B opaque, a raw tail
     schema = [(I, 4), (RAWL, 0), (I, 4), (OPL, 0), (OP, 300), (I, 8), (RAWL, 0)]
     msgs = []
     for a in range(16):
-        for n in lens:
+        for n in LENS:
             v = [a, rng.integers(0, 256, a, dtype=np.uint8).tobytes(), n,
                  rng.integers(0, 256, n, dtype=np.uint8).tobytes(),
                  rng.integers(0, 256, 300, dtype=np.uint8).tobytes(), 700 + a,
                  rng.integers(0, 256, 700 + a, dtype=np.uint8).tobytes()]
             msgs.append(O.xdr_encode(schema, v))
+    return schema, msgs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("method", METHODS)
+def test_gpu_xdr_fast_field_edges(gpu, oracle_mod, method, layout, monkeypatch):
+    """Field lengths around the throughput layout's step-loop threshold
+    (kXdrFastMin = 256: shorter fields take the byte walk, longer ones the
+    1 KiB step loop started from the running register), around the 1 KiB
+    step, the 128-B grid and the loop's ring of loads (LENS), at every start
+    alignment mod 16 (a raw lead-in of 0..15 bytes, so every odd address), and
+    three large fields in one message (the register runs from one step loop
+    into the next): every CRC equal to the oracle's over the hashed stream."""
+    _path(monkeypatch, layout)
+    O = oracle_mod
+    schema, msgs = _once("edges", lambda: _edge_messages(O))
     got = _run(gpu, method, msgs, schema)
-    want = [O.crc(method, O.xdr_hashed_stream(schema, m)) for m in msgs]
-    assert got.tolist() == want
+    assert got.tolist() == _oracle_crcs(O, "edges", method, schema, msgs)
