@@ -69,13 +69,29 @@
  * variable, src/mercury_proc.h:110-122,147-160);
  * mchecksum_gpu_seal_xdr_messages hashes messages already encoded, and
  * mchecksum_gpu_xdr_encoded_sizes gives the message table's lengths.
+ * An overflow RPC -- serialized arguments that do not fit the eager buffer --
+ * keeps its payload in the proc's extra buffer, sent by bulk, while the hash
+ * of that buffer still goes into the HG header of the short eager message
+ * (hg_set_struct, src/mercury.c:699-707 ahead of :715-776):
+ * mchecksum_gpu_seal_detached_messages hashes such payloads where they lie and
+ * stores each value in its message's slot in another buffer, and
+ * mchecksum_gpu_state_seal_messages stores the values of streamed states
+ * (state_init, update_* stages) there.
  *
  * Receiver side: mchecksum_gpu_verify_messages checks received messages in
  * place; mchecksum_gpu_unpack_messages also copies each payload out of the
  * receive buffer to where it is consumed, in the same pass over its bytes
  * (HG_PROC_TYPE on HG_DECODE copies each field out and feeds the same bytes to
  * mchecksum_update, src/mercury_proc.h:124-143,162-181; hg_get_struct then
- * compares, src/mercury.c:565-573).
+ * compares, src/mercury.c:565-573).  For an overflow RPC (HG_CORE_MORE_DATA
+ * set in the core header) the receiver pulls the extra buffer by bulk
+ * (hg_get_extra_payload, src/mercury.c:866-958), decodes from it (:544-546)
+ * and compares its checksum with the eager message's header hash; the bytes
+ * behind the eager message's headers are a bulk descriptor, which that hash
+ * does not cover.  mchecksum_gpu_verify_detached_messages checks a batch of
+ * such RPCs in one call -- the pulled payloads by one table, the hashes read
+ * from the eager messages by another --, and
+ * mchecksum_gpu_state_verify_messages ends a pull that was hashed in stages.
  *
  * Settings: the MCHECKSUM_* environment variables (variants, log level, the
  * MCHECKSUM_GPU_* launch-policy overrides of the A/B tools) are read once,
@@ -397,6 +413,89 @@ MCHECKSUM_PUBLIC int
 mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, uint8_t *dev_status, void *stream);
+
+/* Overflow RPCs: payloads held outside their messages.  "Detached" means that
+ * one table addresses the eager messages -- message i =
+ * dev_msgs[dev_msg_offsets[i], dev_msg_offsets[i+1]): the headers, then
+ * whatever follows them (for Mercury a bulk descriptor, which no hash covers)
+ * -- and a second buffer and table address the payloads: payload i =
+ * dev_payloads[dev_payload_offsets[i], dev_payload_offsets[i+1]), the whole
+ * range (the extra buffer hg_get_extra_payload pulled, or the one
+ * hg_set_struct is about to register).  Both tables hold count + 1
+ * non-decreasing byte offsets.  The hash slot of message i is the 4 bytes at
+ * dev_msg_offsets[i] + hash_offset, network order, at any alignment
+ * (hash_offset = 16 for HG_INPUT without user offset; at most 2^30).  A
+ * message shorter than hash_offset + 4 has no slot: no byte of it is read or
+ * written past its end, and it fails.
+ *
+ *   - Method: a 32-bit model (the slot is 32 bits; crc32c for Mercury).  Every
+ *     other method and every unknown name returns MCHECKSUM_GPU_EMETHOD (so
+ *     would an MSB-first 32-bit model; the catalogue has none).
+ *   - Arguments are checked first (MCHECKSUM_GPU_EINVAL: a NULL required
+ *     pointer with count > 0, count > 2^31, hash_offset > 2^30), then the
+ *     method (_EMETHOD, ahead of the device as in mchecksum_gpu_seal_messages),
+ *     then the device (_ENODEV).  count == 0 needs no buffers, but passes those
+ *     checks first.
+ *   - The payloads are read as in mchecksum_gpu_checksum_offsets (any start
+ *     byte, any size, dev_payloads readable to the next 16-byte boundary); the
+ *     messages are touched only at their slots, byte by byte, so dev_msgs needs
+ *     no padding.
+ *   - Asynchronous and stream-ordered; capture-safe after
+ *     mchecksum_gpu_prepare(); no workspace, nothing allocated on the call path.
+ *   - The two calls over payloads launch twins of the kernels checksum_offsets
+ *     picks for the same count, with its work-queue and static-split rules, and
+ *     fail closed as verify_messages and seal_messages do: a call in which a
+ *     device wait gave up adds 1 -- once -- to the error word, a verify adds
+ *     `count` to *dev_mismatches, and every status the launch cannot vouch for
+ *     is 1 (the slots of such messages are unspecified after a seal).
+ *   - The two state calls end a transfer that was hashed in stages:
+ *     mchecksum_gpu_state_init, then any number of update_offsets,
+ *     update_copy_offsets or update_segments calls, then one of them.  They are
+ *     element kernels like mchecksum_gpu_state_verify: no work-queue slot and no
+ *     device-side wait, so nothing to fail closed on -- and no way to know
+ *     whether an earlier update failed: check the error word first.  The states
+ *     are not modified.
+ *   - DESIGN.md 4.21 has the measurements against the routes through
+ *     verify_offsets, checksum_offsets and state_get. */
+
+/* Receiver: dev_status[i] = 1 and one mismatch added to *dev_mismatches (a
+ * device uint32_t the caller zeroes) when the CRC of payload i differs from
+ * the value in message i's slot, or message i has no slot; else status 0.
+ * Either of the two may be NULL.  Neither buffer is written. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_detached_messages(const char *hash_method,
+    const void *dev_msgs, const uint64_t *dev_msg_offsets, size_t hash_offset,
+    const void *dev_payloads, const uint64_t *dev_payload_offsets,
+    size_t count, uint8_t *dev_status, uint32_t *dev_mismatches, void *stream);
+
+/* Sender: the CRC of payload i is stored big-endian in the 4 slot bytes of
+ * message i and dev_status[i] (optional) = 0; a message without a slot gets
+ * status 1 and no store.  No other byte is written: the bytes behind the
+ * headers keep their values, and dev_payloads is only read. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_detached_messages(const char *hash_method,
+    void *dev_msgs, const uint64_t *dev_msg_offsets, size_t hash_offset,
+    const void *dev_payloads, const uint64_t *dev_payload_offsets,
+    size_t count, uint8_t *dev_status, void *stream);
+
+/* mchecksum_gpu_state_verify with the expected values read from the messages'
+ * slots: the value state_get would return for dev_state[i] (count uint32_t
+ * registers) against message i's slot; verdicts as
+ * mchecksum_gpu_verify_detached_messages. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_verify_messages(const char *hash_method,
+    const void *dev_state, size_t count, const void *dev_msgs,
+    const uint64_t *dev_msg_offsets, size_t hash_offset, uint8_t *dev_status,
+    uint32_t *dev_mismatches, void *stream);
+
+/* Its mirror on the sender: the value state_get would return for dev_state[i]
+ * stored big-endian in message i's slot; statuses and the bytes written as
+ * mchecksum_gpu_seal_detached_messages. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_seal_messages(const char *hash_method,
+    const void *dev_state, size_t count, void *dev_msgs,
+    const uint64_t *dev_msg_offsets, size_t hash_offset, uint8_t *dev_status,
+    void *stream);
 
 /* Pack, hash and seal in one pass over the payload bytes.  Payload i =
  * dev_src[dev_src_offsets[i], dev_src_offsets[i+1]) (the checksum_offsets

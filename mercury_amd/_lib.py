@@ -35,7 +35,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_unpack_xdr_messages", "mchecksum_gpu_pack_xdr_messages",
                "mchecksum_gpu_xdr_encoded_sizes", "mchecksum_gpu_xdr_decoded_sizes",
                "mchecksum_gpu_segment_messages_work_size", "mchecksum_gpu_pack_segment_messages",
-               "mchecksum_gpu_unpack_segment_messages")
+               "mchecksum_gpu_unpack_segment_messages", "mchecksum_gpu_verify_detached_messages",
+               "mchecksum_gpu_seal_detached_messages", "mchecksum_gpu_state_verify_messages",
+               "mchecksum_gpu_state_seal_messages")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -175,6 +177,20 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_seal_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p,
                                               c_void_p]
     L.mchecksum_gpu_seal_messages.restype = c_int
+    # (method, msgs, msg_offsets, hash_offset, payloads, payload_offsets, count, status, [mismatches,] stream)
+    L.mchecksum_gpu_verify_detached_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                         c_size_t, c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_verify_detached_messages.restype = c_int
+    L.mchecksum_gpu_seal_detached_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                       c_size_t, c_void_p, c_void_p]
+    L.mchecksum_gpu_seal_detached_messages.restype = c_int
+    # (method, state, count, msgs, msg_offsets, hash_offset, status, [mismatches,] stream)
+    L.mchecksum_gpu_state_verify_messages.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                      c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_state_verify_messages.restype = c_int
+    L.mchecksum_gpu_state_seal_messages.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                    c_void_p, c_void_p]
+    L.mchecksum_gpu_state_seal_messages.restype = c_int
     L.mchecksum_gpu_pack_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                               c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_pack_messages.restype = c_int

@@ -391,9 +391,11 @@ template <bool LIGHT>
 constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 
 // OP (launch_plan.h, BatchOp): what the owning lane does with a payload's CRC.
-template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false>
+// DETACHED (launch_plan.h, KernelKey::detached): a verify's or a seal's hash
+// slots lie in the eager messages, a buffer and table of their own.
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, bool DETACHED = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false}), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED}), "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
@@ -483,6 +485,29 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                     // here, and whole-piece stores only inside a payload)
                     if (!misfit) store_be32(msg + a.hash_off, x ^ xorout);
                     if (a.status) a.status[p] = misfit ? 1 : 0;
+                }
+                return;
+            }
+            if constexpr (DETACHED) {
+                // The payload is the whole of [m0, m1); its hash slot is in eager
+                // message p of another buffer (`out`, by the table dst_offsets),
+                // four bytes at any alignment -- the in-place epilogues below at
+                // another address (launch_plan.h: msg_slot_ok, msg_slot_at).  A
+                // verify reads `out` only.
+                const uint64_t h0 = a.dst_offsets[p], h1 = a.dst_offsets[p + 1], n = m1 - m0;
+                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + m0, n, gl, lc0, lc1)
+                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + m0, n, gl, lc0, lc1);
+                if (gl == 0) {
+                    const bool short_msg = !mck::msg_slot_ok(h0, h1, a.hash_off);
+                    uint8_t *slot = reinterpret_cast<uint8_t *>(a.out) + mck::msg_slot_at(h0, a.hash_off);
+                    if constexpr (SEAL) {
+                        if (!short_msg) store_be32(slot, x ^ xorout);
+                        if (a.status) a.status[p] = short_msg ? 1 : 0;
+                    } else {
+                        const bool bad = short_msg || load_be32(slot) != (x ^ xorout);
+                        if (a.status) a.status[p] = bad ? 1 : 0;
+                        nbad += bad;
+                    }
                 }
                 return;
             }

@@ -261,15 +261,37 @@ enum BatchOp : int {
     kOpUnpack,
 };
 
+// Where a verify's or a seal's hash slot is.  In place (false): in the buffer
+// the payloads are in, headers then payload, one table.  Detached (true): an
+// overflow RPC -- the table (base, offsets) addresses the payloads alone, and
+// the slots are in the eager messages, another buffer (BatchArgs::out) with a
+// table of its own (dst_offsets): mchecksum_gpu_verify_detached_messages,
+// mchecksum_gpu_seal_detached_messages.  A key field beside the operation, not
+// an operation: the epilogue is kOpVerify's or kOpSeal's, at another address.
+//
+// The slot rule of the detached calls (and of state_verify_messages and
+// state_seal_messages, which end a streamed pull with the same epilogue):
+// message [m0, m1) carries its slot iff it holds hash_off + 4 bytes -- a table
+// that runs backwards never does --, and the slot's four bytes start hash_off
+// bytes in.  A message without its slot is never read or written: verify
+// counts it as a mismatch, seal gives it status 1.
+MCK_HOST_DEVICE_INLINE bool msg_slot_ok(uint64_t m0, uint64_t m1, uint64_t hash_off) {
+    return m1 >= m0 && m1 - m0 >= hash_off && m1 - m0 - hash_off >= 4;
+}
+MCK_HOST_DEVICE_INLINE uint64_t msg_slot_at(uint64_t m0, uint64_t hash_off) { return m0 + hash_off; }
+// hash_offset is carried in 32 bits (BatchArgs::hash_off), capped as payload_offset is
+constexpr uint64_t kMaxHashOff = 1ull << 30;
+
 // One instantiation of the batch kernels (crc32c_batch_kernel,
 // crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
 struct KernelKey {
     int width, lg, mode, op;
     bool nt, light, split;
+    bool detached = false;
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split;
+           a.split == b.split && a.detached == b.detached;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -277,6 +299,8 @@ constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
 constexpr bool kernel_key_valid(const KernelKey &k) {
     if ((k.width != 32 && k.width != 64) || k.lg < 0 || k.lg > CRC_GPU_MAX_LOG2G) return false;
     if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
+    // detached: the message verify and seal of the CRC-32C offsets kernels (light, full, non-temporal)
+    if (k.detached && (k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
     if (k.split)  // pieces of aligned CRC-64 payloads, 64 lanes each: checksums only
         return k.width == 64 && k.mode == kFixedAligned && k.lg == CRC_GPU_MAX_LOG2G && k.op == kOpChecksum;
     switch (k.mode) {
@@ -299,9 +323,9 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
-inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op) {
-    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split};
-    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true};
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, bool detached = false) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached};
+    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached};
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;
     if (k.light || k.mode == kFixedGeneric) k.nt = false;

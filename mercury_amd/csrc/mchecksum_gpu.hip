@@ -340,11 +340,11 @@ struct KLaunch {
 };
 
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
-template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT>
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, bool DETACHED>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT})) {
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED})) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
-        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT>, S::block, S::blocks_per_cu};
+        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, DETACHED>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
     return {};
@@ -368,7 +368,10 @@ KLaunch kernel_for(const KernelKey &k) {
                     return lift<2>(k.nt, [&](auto nt) {
                         return lift<2>(k.light, [&](auto light) {
                             return lift<2>(k.split, [&](auto split) {
-                                return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0, split() != 0>();
+                                return lift<2>(k.detached, [&](auto det) {
+                                    return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0, split() != 0,
+                                                      det() != 0>();
+                                });
                             });
                         });
                     });
@@ -395,6 +398,11 @@ struct OffsetsCall {
     bool msg = false;                    // message mode: payload_offset, hash_offset
     size_t pay_off = 0, hash_off = 0;
     void *stream = nullptr;
+    // detached verify and seal (launch_plan.h, KernelKey::detached): src holds the payloads alone, and the
+    // hash slots lie hash_off bytes into the eager messages hdr[hdr_off[i], hdr_off[i + 1])
+    bool detached = false;
+    void *hdr = nullptr;
+    const uint64_t *hdr_off = nullptr;
 };
 
 // The front of every offsets-shaped entry point: argument checks, model,
@@ -402,20 +410,23 @@ struct OffsetsCall {
 // HG messages (seal, pack, unpack) check the method ahead of the device, as an
 // argument (as verify_core_headers does); the others the device first.
 int offsets_call(const OffsetsCall &c) {
-    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal;
-    const bool stores = c.op == kOpChecksum || c.op == kOpUpdate || c.op == kOpSeal;
+    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal || c.detached;
+    const bool stores = c.op == kOpChecksum || c.op == kOpUpdate || (c.op == kOpSeal && !c.detached);
     // an empty batch needs no buffers (not even the one-entry offsets table)
     if (c.count && (!c.src || !c.src_off || (stores && !c.out) || (copies && (!c.dst || !c.dst_off)) ||
-                    (c.op == kOpVerify && !c.msg && !c.expected)))
+                    (c.detached && (!c.hdr || !c.hdr_off)) || (c.op == kOpVerify && !c.msg && !c.detached && !c.expected)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (c.msg && (c.hash_off + 4 > c.pay_off || c.pay_off > (1u << 30)))
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
+    if (c.detached && c.hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
     if ((uint64_t)c.count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
     Model m;
     int rc;
     if (hg) {
         if ((rc = resolve_model(c.method, &m))) return rc;
         if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
+        // the detached epilogue stores and compares x ^ xorout unswapped: reflected models (both 32-bit ones are)
+        if (c.detached && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no detached message kernel");
     }
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
     if (!hg && (rc = resolve_model(c.method, &m))) return rc;
@@ -429,14 +440,16 @@ int offsets_call(const OffsetsCall &c) {
     if (c.count == 0) return MCHECKSUM_GPU_OK;
     if (c.msg && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const KLaunch k = kernel_for(kernel_key(p, c.op));
+    const KLaunch k = kernel_for(kernel_key(p, c.op, c.detached));
     if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     BatchArgs a{};
     a.base = (const uint8_t *)c.src;
     a.offsets = c.src_off;
     a.count = c.count;
-    a.out = copies ? c.dst : c.out;
+    // (a detached verify or seal stores no values and copies nothing: `out` and the union are free for the messages)
+    a.out = copies ? c.dst : c.detached ? c.hdr : c.out;
     if (copies) a.dst_offsets = c.dst_off;
+    else if (c.detached) a.dst_offsets = c.hdr_off;
     else a.expected = c.expected;
     a.status = c.status;
     a.mismatches = c.mismatches;
@@ -574,6 +587,31 @@ __global__ __launch_bounds__(256) void state_verify_kernel(const T *st, const T 
         nbad += mck::seg_verify_decide(false, v, expected[i], status, i);
     }
     add_mismatches(mism, nbad);  // once per workgroup (crc_gpu_common.h)
+}
+
+// state_verify with the expected values read from the eager messages' hash
+// slots, and its mirror on the sender (SEAL): the end of a streamed pull or
+// push of overflow payloads.  The slot rule is the detached kernels'
+// (launch_plan.h: msg_slot_ok, msg_slot_at); 32-bit models only, all of them
+// reflected, so the value is the register ^ xorout.  The states are only read.
+template <bool SEAL>
+__global__ __launch_bounds__(256) void state_messages_kernel(const uint32_t *st, uint64_t n, uint32_t xorout, uint8_t *msgs,
+                                                             const uint64_t *msg_off, uint32_t hash_off, uint8_t *status,
+                                                             uint32_t *mism) {
+    uint32_t nbad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t m0 = msg_off[i], m1 = msg_off[i + 1];
+        const bool short_msg = !mck::msg_slot_ok(m0, m1, hash_off);
+        uint8_t *slot = msgs + mck::msg_slot_at(m0, hash_off);
+        const uint32_t v = mck_reg_to_crc32(st[i], xorout, 0);
+        if constexpr (SEAL) {
+            if (!short_msg) store_be32(slot, v);
+            if (status) status[i] = short_msg ? 1 : 0;
+        } else {
+            nbad += mck::seg_verify_decide(short_msg, v, short_msg ? 0 : load_be32(slot), status, i);
+        }
+    }
+    if constexpr (!SEAL) add_mismatches(mism, nbad);  // once per workgroup (crc_gpu_common.h)
 }
 
 // out may alias a or b, element for element
@@ -774,6 +812,32 @@ int state_call(const char *method, size_t count, Model *m, crc_rmodel_t *rm, Dev
     return rc;
 }
 
+// state_verify_messages and state_seal_messages: arguments, then the method
+// (a 32-bit model, ahead of the device, as the calls on HG messages check
+// it), then the device.  An element kernel: no work-queue slot, no workspace,
+// no device-side wait.
+int state_messages_call(bool seal, const char *method, const void *dev_state, size_t count, void *dev_msgs,
+                        const uint64_t *dev_msg_offsets, size_t hash_off, uint8_t *status, uint32_t *mism, void *stream) {
+    if (count && (!dev_state || !dev_msgs || !dev_msg_offsets)) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
+    if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
+    Model m;
+    if (int rc = resolve_model(method, &m)) return rc;
+    if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
+    // state_messages_kernel takes the value as register ^ xorout, unswapped: reflected models (both 32-bit ones are)
+    if (m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no state message kernel");
+    if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
+    DevCtx *c = nullptr;
+    if (int rc = device_ctx(&c)) return rc;
+    if (count == 0) return MCHECKSUM_GPU_OK;
+    const crc_rmodel_t rm = gpu_rmodel(m.idx);
+    const dim3 grid(elem_grid(count)), block(256);
+    const hipError_t e = launch_kernel(seal ? state_messages_kernel<true> : state_messages_kernel<false>, grid, block,
+                                       (hipStream_t)stream, nullptr, (const uint32_t *)dev_state, (uint64_t)count,
+                                       (uint32_t)rm.xorout, (uint8_t *)dev_msgs, dev_msg_offsets, (uint32_t)hash_off, status, mism);
+    return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, seal ? "state seal" : "state verify");
+}
+
 int launch_fixed(DevCtx *c, const Model &m, const LaunchPlan &p, const void *pack, const void *dev_base, size_t stride,
                  size_t len, size_t count, void *dev_out, void *stream) {
     BatchArgs a{};
@@ -957,6 +1021,50 @@ int mchecksum_gpu_unpack_messages(const char *hash_method, const void *dev_buf, 
     c.mismatches = dev_mismatches;
     c.stream = stream;
     return offsets_call(c);
+}
+
+int mchecksum_gpu_verify_detached_messages(const char *hash_method, const void *dev_msgs, const uint64_t *dev_msg_offsets,
+                                           size_t hash_offset, const void *dev_payloads,
+                                           const uint64_t *dev_payload_offsets, size_t count, uint8_t *dev_status,
+                                           uint32_t *dev_mismatches, void *stream) {
+    // an overflow RPC: the payloads are the batch, the eager messages only carry the hashes (and are only read)
+    OffsetsCall c{kOpVerify, hash_method, dev_payloads, dev_payload_offsets, count};
+    c.detached = true;
+    c.hdr = const_cast<void *>(dev_msgs);
+    c.hdr_off = dev_msg_offsets;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_mismatches;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_seal_detached_messages(const char *hash_method, void *dev_msgs, const uint64_t *dev_msg_offsets,
+                                         size_t hash_offset, const void *dev_payloads,
+                                         const uint64_t *dev_payload_offsets, size_t count, uint8_t *dev_status,
+                                         void *stream) {
+    OffsetsCall c{kOpSeal, hash_method, dev_payloads, dev_payload_offsets, count};
+    c.detached = true;
+    c.hdr = dev_msgs;
+    c.hdr_off = dev_msg_offsets;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_state_verify_messages(const char *hash_method, const void *dev_state, size_t count,
+                                        const void *dev_msgs, const uint64_t *dev_msg_offsets, size_t hash_offset,
+                                        uint8_t *dev_status, uint32_t *dev_mismatches, void *stream) {
+    return state_messages_call(false, hash_method, dev_state, count, const_cast<void *>(dev_msgs), dev_msg_offsets,
+                               hash_offset, dev_status, dev_mismatches, stream);
+}
+
+int mchecksum_gpu_state_seal_messages(const char *hash_method, const void *dev_state, size_t count, void *dev_msgs,
+                                      const uint64_t *dev_msg_offsets, size_t hash_offset, uint8_t *dev_status,
+                                      void *stream) {
+    return state_messages_call(true, hash_method, dev_state, count, dev_msgs, dev_msg_offsets, hash_offset, dev_status,
+                               nullptr, stream);
 }
 
 int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {

@@ -613,6 +613,118 @@ def pack_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: torch.Tens
     return status
 
 
+def _check_detached(msgs, msg_offsets, offsets_host, hash_offset: int) -> int:
+    """The eager messages of a detached call; returns count."""
+    _check_device_u8(msgs, "msgs")
+    _check_offsets(msgs, msg_offsets, offsets_host)
+    if hash_offset < 0 or hash_offset > 1 << 30:
+        raise GpuChecksumError("hash_offset must lie in 0..2^30")
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    return count
+
+
+def _seal_status(msgs: torch.Tensor, count: int, status):
+    """_sender_status, with False for no status array at all."""
+    return False if status is False else _sender_status(msgs, count, status)
+
+
+def verify_detached_messages(msgs: torch.Tensor, msg_offsets: torch.Tensor, payloads: torch.Tensor,
+                             payload_offsets: torch.Tensor, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                             offsets_host=None, payload_offsets_host=None, status=None, mismatches=None):
+    """Verify overflow RPCs (mchecksum_gpu_verify_detached_messages): payload
+    i = payloads[payload_offsets[i] : payload_offsets[i+1]] lies outside its
+    message, and the expected CRC is the network-order u32 at msg_offsets[i] +
+    hash_offset of `msgs`, the eager messages.  Returns (status uint8 per
+    message: 1 = the CRC differs or the message is shorter than hash_offset +
+    4, mismatch count tensor).  status / mismatches: None allocates, False
+    leaves that output out, a tensor is reused (the count is added to).
+    Nothing is written to either buffer.  offsets_host / payload_offsets_host
+    (host copies) have the tables validated before launch."""
+    count = _check_detached(msgs, msg_offsets, offsets_host, hash_offset)
+    _check_device_u8(payloads, "payloads")
+    _check_offsets(payloads, payload_offsets, payload_offsets_host)
+    if payload_offsets.numel() != count + 1:
+        raise GpuChecksumError("msg_offsets and payload_offsets need the same number (>= 1) of entries")
+    status, mism = _verdict_buffers(count, msgs.device, status, mismatches)
+    _same_device(msgs, msg_offsets=msg_offsets, payloads=payloads, payload_offsets=payload_offsets,
+                 status=None if status is False else status, mismatches=None if mism is False else mism)
+    with _on(msgs):
+        rc = _lib().mchecksum_gpu_verify_detached_messages(method.encode(), msgs.data_ptr(), msg_offsets.data_ptr(),
+                                                           hash_offset, payloads.data_ptr(), payload_offsets.data_ptr(),
+                                                           count, _ptr(status), _ptr(mism),
+                                                           _stream_handle(stream, msgs.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_detached_messages")
+    return status, mism
+
+
+def seal_detached_messages(msgs: torch.Tensor, msg_offsets: torch.Tensor, payloads: torch.Tensor,
+                           payload_offsets: torch.Tensor, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                           offsets_host=None, payload_offsets_host=None, status=None):
+    """Sender side of verify_detached_messages: store the CRC of payload i
+    network-order in the 4 bytes at msg_offsets[i] + hash_offset of `msgs`.
+    Returns status (uint8 per message: 1 = shorter than hash_offset + 4, not
+    written; False passes none and returns False).  Only those 4 bytes of each
+    sealed message are written; `payloads` is only read."""
+    count = _check_detached(msgs, msg_offsets, offsets_host, hash_offset)
+    _check_device_u8(payloads, "payloads")
+    _check_offsets(payloads, payload_offsets, payload_offsets_host)
+    if payload_offsets.numel() != count + 1:
+        raise GpuChecksumError("msg_offsets and payload_offsets need the same number (>= 1) of entries")
+    status = _seal_status(msgs, count, status)
+    _same_device(msgs, msg_offsets=msg_offsets, payloads=payloads, payload_offsets=payload_offsets,
+                 status=None if status is False else status)
+    with _on(msgs):
+        rc = _lib().mchecksum_gpu_seal_detached_messages(method.encode(), msgs.data_ptr(), msg_offsets.data_ptr(),
+                                                         hash_offset, payloads.data_ptr(), payload_offsets.data_ptr(),
+                                                         count, _ptr(status), _stream_handle(stream, msgs.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_detached_messages")
+    return status
+
+
+def state_verify_messages(state: torch.Tensor, msgs: torch.Tensor, msg_offsets: torch.Tensor, hash_offset: int = 16,
+                          method: str = "crc32c", stream=None, offsets_host=None, status=None, mismatches=None):
+    """state_verify with the expected values read from the eager messages'
+    hash slots (mchecksum_gpu_state_verify_messages): the end of a pull hashed
+    in stages (state_init, then update_offsets / update_copy_offsets / segment
+    updates).  Returns (status, mismatch count) as verify_detached_messages;
+    the states are left as they are.  It cannot know whether an earlier update
+    failed: check the error word first."""
+    count = _check_detached(msgs, msg_offsets, offsets_host, hash_offset)
+    _check_state(state, method, count, "state")
+    status, mism = _verdict_buffers(count, msgs.device, status, mismatches)
+    _same_device(msgs, msg_offsets=msg_offsets, state=state, status=None if status is False else status,
+                 mismatches=None if mism is False else mism)
+    with _on(msgs):
+        rc = _lib().mchecksum_gpu_state_verify_messages(method.encode(), state.data_ptr(), count, msgs.data_ptr(),
+                                                        msg_offsets.data_ptr(), hash_offset, _ptr(status), _ptr(mism),
+                                                        _stream_handle(stream, msgs.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_verify_messages")
+    return status, mism
+
+
+def state_seal_messages(state: torch.Tensor, msgs: torch.Tensor, msg_offsets: torch.Tensor, hash_offset: int = 16,
+                        method: str = "crc32c", stream=None, offsets_host=None, status=None):
+    """The sender's mirror of state_verify_messages: store the CRC each state
+    has reached network-order in its message's hash slot.  Returns status as
+    seal_detached_messages; the states are left as they are."""
+    count = _check_detached(msgs, msg_offsets, offsets_host, hash_offset)
+    _check_state(state, method, count, "state")
+    status = _seal_status(msgs, count, status)
+    _same_device(msgs, msg_offsets=msg_offsets, state=state, status=None if status is False else status)
+    with _on(msgs):
+        rc = _lib().mchecksum_gpu_state_seal_messages(method.encode(), state.data_ptr(), count, msgs.data_ptr(),
+                                                      msg_offsets.data_ptr(), hash_offset, _ptr(status),
+                                                      _stream_handle(stream, msgs.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_seal_messages")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its
