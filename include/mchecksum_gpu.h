@@ -829,6 +829,93 @@ mchecksum_gpu_seal_core_headers(const char *hash_method, int kind,
     void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
     uint8_t *dev_status, void *stream);
 
+/* Whole RPC messages: the core header, its flags and the payload in one pass.
+ * A receiver that drains a multi-recv buffer checks the core header's CRC-16
+ * (hg_core_header_request_proc / _response_proc), then reads the header's
+ * flags -- with HG_CORE_MORE_DATA (src/mercury_core.h:75, bit 0) the payload
+ * is not in the message: it is pulled by bulk and checked later against the
+ * same HG slot --, and only otherwise compares the CRC of the bytes behind the
+ * headers with the HG header's hash (src/mercury_core.c:4754-4828,
+ * src/mercury.c:473-594).  mchecksum_gpu_verify_core_headers and
+ * mchecksum_gpu_verify_messages are the first and the third step in a launch
+ * each; the second knows nothing of flags, so it reports a checksum error for
+ * an overflow RPC (it hashes the bulk descriptor) and vouches for a payload
+ * whose header is corrupt.  These two calls treat a message as Mercury does.
+ *
+ * Message i = dev_buf[dev_msg_offsets[i], dev_msg_offsets[i+1]), count + 1
+ * table entries, L its length; a table that runs backwards counts as L = 0.
+ * `kind` names the core header's layout, as for the core-header calls:
+ *     request : 12 hashed host-order bytes, flags = byte 10, hash big-endian at 12
+ *     response:  4 hashed host-order bytes, flags = byte  1, hash big-endian at  4
+ * payload_offset and hash_offset are mchecksum_gpu_verify_messages'.
+ *
+ *   - header_method: a 16-bit model, either bit order ("crc16");
+ *     payload_method: a reflected 32-bit model ("crc32c").
+ *   - Arguments are checked first (MCHECKSUM_GPU_EINVAL: a NULL required
+ *     pointer with count > 0, an unknown kind, count > 2^31, hash_offset < 16,
+ *     hash_offset + 4 > payload_offset, hash_offset > 2^30), then the methods
+ *     (_EMETHOD: a header_method that is not a 16-bit model, a payload_method
+ *     that is not a reflected 32-bit one, an unknown name), then the device
+ *     (_ENODEV).  count == 0 needs no buffers, but passes those checks first.
+ *   - Read, launch and capture rules of verify_messages / seal_messages: any
+ *     start byte, dev_buf readable to the next 16-byte boundary, payloads of
+ *     any size; asynchronous and stream-ordered; capture-safe after
+ *     mchecksum_gpu_prepare() of BOTH methods (a replay reads the buffer's and
+ *     the table's current contents); no workspace, nothing allocated on the
+ *     call path; one launch, a twin of the kernel verify_messages picks for the
+ *     same count.
+ *   - Fail closed: a call in which a device wait gave up adds 1 -- once -- to
+ *     the error word and to mchecksum_gpu_queue_faults(), every status it
+ *     cannot vouch for is MCHECKSUM_GPU_RPC_FAULT, and a verify adds `count` to
+ *     dev_counts[MCHECKSUM_GPU_RPC_FAULT].  No message that fails a rule reads
+ *     OK or DEFERRED; the sealed bytes of a FAULT message are unspecified.
+ *   - DESIGN.md 4.22 has the design and the measurements against the two-call
+ *     route. */
+#define MCHECKSUM_GPU_RPC_OK       0  /* header good, payload good */
+#define MCHECKSUM_GPU_RPC_PAYLOAD  1  /* header good, eager, payload CRC differs */
+#define MCHECKSUM_GPU_RPC_HEADER   2  /* core header CRC-16 differs */
+#define MCHECKSUM_GPU_RPC_SHORT    3  /* no whole core header, or eager and shorter
+                                         than payload_offset */
+#define MCHECKSUM_GPU_RPC_DEFERRED 4  /* header good, MORE_DATA set: payload elsewhere,
+                                         nothing hashed or compared here */
+#define MCHECKSUM_GPU_RPC_FAULT    5  /* the launch cannot vouch for this message */
+#define MCHECKSUM_GPU_RPC_CLASSES  6
+
+/* Receiver.  dev_status[i] is the first rule that matches:
+ *   1. L < 16                                              -> SHORT
+ *   2. the CRC-16 of the field image differs from the hash -> HEADER (whatever
+ *      the flags say: the flags byte is inside the image)
+ *   3. MORE_DATA set -> DEFERRED: no byte behind the core header is looked at,
+ *      L may be anything >= 16; whether the HG slot exists is
+ *      mchecksum_gpu_verify_detached_messages' rule, later
+ *   4. L < payload_offset                                  -> SHORT
+ *   5. the CRC of [payload_offset, L) differs from the network-order u32 at
+ *      hash_offset                                         -> PAYLOAD
+ *   6. OK
+ * dev_counts: MCHECKSUM_GPU_RPC_CLASSES device uint32_t words the caller
+ * zeroes; dev_counts[k] grows by the number of messages of status k.  Either of
+ * dev_status and dev_counts may be NULL.  dev_buf is never written. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_rpc_messages(const char *header_method,
+    const char *payload_method, int kind, const void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+/* Sender: the caller has filled every header byte except the two hashes.
+ *   L < 16                                 -> SHORT, nothing written
+ *   MORE_DATA clear, L < payload_offset    -> SHORT, nothing written (Mercury
+ *                                             never sends such a message)
+ *   MORE_DATA clear otherwise              -> the payload CRC big-endian at
+ *       hash_offset and the header CRC-16 big-endian at 12 / 4; status OK
+ *   MORE_DATA set                          -> the header CRC-16 alone; status
+ *       DEFERRED (the HG slot is mchecksum_gpu_seal_detached_messages')
+ * Exactly those 2 or 6 bytes of a message are written, no others. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_rpc_messages(const char *header_method,
+    const char *payload_method, int kind, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
 /* XDR-mode proc checksum.  In a Mercury built with
  * MERCURY_USE_XDR (HG_HAS_XDR) the serialized buffer holds XDR -- every
  * integer big-endian and rounded up to 4 bytes, byte arrays zero-padded to a

@@ -390,12 +390,50 @@ __device__ __forceinline__ uint32_t payload32_g64(TAB lds, const crc32_gpu_pack_
 template <bool LIGHT>
 constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 
+// ---- whole RPC messages (KernelKey::rpc) ----
+// The header pack's rows through a global pointer (a flat load would also count against the LDS waits).
+typedef const __attribute__((address_space(1))) uint16_t *rpc_tab_t;
+
+// A verifying workgroup's per-class counts: LDS atomics by the owning lanes
+// (none returns a value or leaves the CU), added to the caller's six words
+// once per WORKGROUP at its end, as add_mismatches adds its one.  The batch
+// kernels' LDS has room for these 24 bytes, not for a table.
+__device__ __forceinline__ uint32_t *rpc_wg_counts() {
+    __shared__ uint32_t wg_cls[mck::kRpcClasses];
+    return wg_cls;
+}
+// Every thread of the workgroup calls this, once (counters zeroed ahead of the fill's barrier).
+__device__ __forceinline__ void rpc_add_counts(uint32_t *ctr) {
+    __syncthreads();
+    if (threadIdx.x < mck::kRpcClasses && ctr) {
+        const uint32_t v = rpc_wg_counts()[threadIdx.x];
+        if (v) atomicAdd(&ctr[threadIdx.x], v);
+    }
+}
+// fail_closed's sibling for the RPC twins: the caller's error word gets +1, a
+// verify adds `count` to the FAULT class, and every status becomes FAULT --
+// verify's and seal's, so a stale OK or DEFERRED in the caller's buffer never
+// survives; messages hashed after the sweep overwrite theirs with the truth.
+template <bool VERIFY>
+__device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    if (lane == 0) {
+        if (a.err_word) atomicAdd(a.err_word, 1u);
+        if (VERIFY && a.mismatches) atomicAdd(&a.mismatches[mck::kRpcFault], (uint32_t)a.count);
+    }
+    if (a.status)
+        for (uint64_t p = lane; p < a.count; p += 64) a.status[p] = (uint8_t)mck::kRpcFault;
+}
+
 // OP (launch_plan.h, BatchOp): what the owning lane does with a payload's CRC.
 // DETACHED (launch_plan.h, KernelKey::detached): a verify's or a seal's hash
 // slots lie in the eager messages, a buffer and table of their own.
-template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, bool DETACHED = false>
+// RPC (KernelKey::rpc): a verify or a seal of whole RPC messages -- the core
+// header's CRC-16 and its flags decide with the payload's CRC what a message
+// is (launch_plan.h: rpc_verify_class, rpc_seal_class).
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, bool DETACHED = false, bool RPC = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED}), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED, RPC}), "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
@@ -425,6 +463,18 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     // barrier they became a vector load per payload whose wait, merged with
     // the ring's at the prefetch branch, cost a vmcnt(0) per payload)
     const uint32_t init = pk->init, xorout = pk->xorout;
+    // RPC: the header model's pack rides in the `expected` pointer, which a
+    // verify by header and a seal leave free (two scalar loads, here for the
+    // reason above)
+    [[maybe_unused]] rpc_tab_t rpc_tab = nullptr;
+    [[maybe_unused]] uint32_t rpc_kind = 0, rpc_c = 0;
+    if constexpr (RPC) {
+        const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(a.expected);
+        rpc_tab = (rpc_tab_t)uniform64(reinterpret_cast<uint64_t>(&hp->row[0][0]));
+        rpc_kind = hp->kind;
+        rpc_c = hp->c;
+        if (VERIFY && threadIdx.x < mck::kRpcClasses) rpc_wg_counts()[threadIdx.x] = 0;  // (ahead of the fill's barrier)
+    }
     uint4 ring0[kRing];
     const bool pre = PRE && wave < units;
     if (DYN && threadIdx.x == 0) wg_queue_init(&wgq, a.queue, units);
@@ -488,6 +538,51 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 }
                 return;
             }
+            if constexpr (RPC) {
+                // A whole RPC message.  Lanes 0..15 load a header byte each and
+                // look up its term of the CRC-16 (launch_plan.h, RpcHdrPack:
+                // one load, no chain, and in flight under the payload loop).
+                // The flags byte, from its lane, and the length decide for the
+                // whole wave whether the payload is hashed -- ahead of the first
+                // payload load; otherwise the wave hashes an empty payload.
+                // `len` (a fixed batch's field) carries payload_offset in 64 bits.
+                const uint64_t L = mck::rpc_len(m0, m1), pay = a.len;
+                const bool whole = L >= mck::kRpcHdrBytes;
+                uint32_t hb = 0, term = 0;
+                if (whole && lane < mck::kRpcHdrBytes) hb = global_ptr(a.base + m0, true)[lane];
+                const bool more = whole && (__builtin_amdgcn_readlane(hb, mck::rpc_flags_at(rpc_kind)) & 1u);
+                if (whole && lane < mck::kRpcHdrBytes) term = rpc_tab[mck::rpc_hdr_term_index(rpc_kind, lane, hb)];
+                const bool hashed = mck::rpc_hashes_payload(L, more, pay);
+                const uint64_t o = hashed ? m0 + pay : m0 + L, n = m0 + L - o;
+                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
+                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
+                // the image's terms XOR over the lanes that hold them; the wire hash is two identity terms
+                uint32_t t = lane < mck::rpc_img_bytes(rpc_kind) ? term : 0u;
+#pragma unroll
+                for (int d = 1; d < 16; d <<= 1) t ^= __shfl_xor(t, d, 64);
+                const uint32_t crc16 = mck::rpc_hdr_crc(rpc_c, __builtin_amdgcn_readfirstlane(t));
+                const uint32_t hat = mck::rpc_hash_at(rpc_kind);
+                const uint32_t wire = __builtin_amdgcn_readlane(term, hat) << 8 | __builtin_amdgcn_readlane(term, hat + 1);
+                if (gl == 0) {
+                    if constexpr (SEAL) {
+                        // (byte stores: the 2 or 6 bytes share their granules with other fields and messages)
+                        uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + m0;
+                        const uint32_t cls = mck::rpc_seal_class(L, more, pay);
+                        if (cls == mck::kRpcOk) store_be32(msg + a.hash_off, x ^ xorout);
+                        if (cls != mck::kRpcShort) {
+                            msg[hat] = (uint8_t)(crc16 >> 8);
+                            msg[hat + 1] = (uint8_t)crc16;
+                        }
+                        if (a.status) a.status[p] = (uint8_t)cls;
+                    } else {
+                        const bool pay_ok = hashed && load_be32(a.base + m0 + a.hash_off) == (x ^ xorout);
+                        const uint32_t cls = mck::rpc_verify_class(L, crc16 == wire, more, pay, pay_ok);
+                        if (a.status) a.status[p] = (uint8_t)cls;
+                        atomicAdd(&rpc_wg_counts()[cls], 1u);  // LDS; the device's counters once per workgroup
+                    }
+                }
+                return;
+            }
             if constexpr (DETACHED) {
                 // The payload is the whole of [m0, m1); its hash slot is in eager
                 // message p of another buffer (`out`, by the table dst_offsets),
@@ -546,13 +641,17 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
         };
         if constexpr (!LIGHT) {
             // (a sealing launch sweeps its statuses as a verify does, with no counter to add to)
-            if (for_each_unit<true>(&wgq, a.queue, units, wave, nw, one)) fail_closed<VERIFY || SEAL>(a);
+            if (for_each_unit<true>(&wgq, a.queue, units, wave, nw, one)) {
+                if constexpr (RPC) rpc_fail_closed<VERIFY>(a);
+                else fail_closed<VERIFY || SEAL>(a);
+            }
         } else {  // static: a byte-balanced contiguous range per wave
             uint64_t first, last;
             wave_range(a.offsets, a.count, wave, nw, &first, &last);
             for (uint64_t p = first; p < last; p++) one(p);
         }
-        if constexpr (VERIFY) add_mismatches(a.mismatches, nbad);
+        if constexpr (RPC && VERIFY) rpc_add_counts(a.mismatches);
+        else if constexpr (VERIFY) add_mismatches(a.mismatches, nbad);
         MCK_STAMP(wave, 2);
         return;
     }

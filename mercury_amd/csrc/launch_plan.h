@@ -282,16 +282,121 @@ MCK_HOST_DEVICE_INLINE uint64_t msg_slot_at(uint64_t m0, uint64_t hash_off) { re
 // hash_offset is carried in 32 bits (BatchArgs::hash_off), capped as payload_offset is
 constexpr uint64_t kMaxHashOff = 1ull << 30;
 
+// ---- whole RPC messages: mchecksum_gpu_verify_rpc_messages, _seal_rpc_messages ----
+//
+// A message is a 16-byte core header (src/mercury_core_header.c:175-289), the
+// HG header with the payload hash at hash_off, and from pay_off the payload.
+// The core header's CRC-16 runs over the host-order field image, 12 bytes of a
+// request and 4 of a response; bit 0 of its flags byte is HG_CORE_MORE_DATA
+// (src/mercury_core.h:75): the payload is then elsewhere, and neither hashed
+// nor compared here.  The rules below are the kernels' (crc_gpu_crc32.h, RPC)
+// and the CPU's (tests/native/rpc_msg.cpp): the same code.
+constexpr uint64_t kRpcHdrBytes = 16;
+// (MCHECKSUM_GPU_CORE_HEADER_REQUEST / _RESPONSE and MCHECKSUM_GPU_RPC_*; mchecksum_gpu.hip asserts they agree)
+constexpr uint32_t kRpcRequest = 0, kRpcResponse = 1;
+enum RpcClass : uint32_t { kRpcOk = 0, kRpcPayload, kRpcHeader, kRpcShort, kRpcDeferred, kRpcFault, kRpcClasses };
+
+// A table that runs backwards holds an empty message.
+MCK_HOST_DEVICE_INLINE uint64_t rpc_len(uint64_t m0, uint64_t m1) { return m1 >= m0 ? m1 - m0 : 0; }
+// Bytes of the hashed image, and where on the wire the flags byte and the big-endian header hash lie.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_img_bytes(uint32_t kind) { return kind == kRpcRequest ? 12u : 4u; }
+MCK_HOST_DEVICE_INLINE uint32_t rpc_flags_at(uint32_t kind) { return kind == kRpcRequest ? 10u : 1u; }
+MCK_HOST_DEVICE_INLINE uint32_t rpc_hash_at(uint32_t kind) { return kind == kRpcRequest ? 12u : 4u; }
+// Wire byte j < rpc_img_bytes of the header is byte rpc_img_index of the image:
+// the request's id (wire 2..9, big-endian) and the response's cookie (wire
+// 2..3) are hashed as little-endian host values, every other field is a byte.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_img_index(uint32_t kind, uint32_t j) {
+    if (kind == kRpcRequest) return j >= 2 && j < 10 ? 11u - j : j;
+    return j >= 2 ? 5u - j : j;
+}
+
+// The CRC-16 of so short an image, by position: a CRC register after n bytes
+// is Z^n(init) ^ XOR_i Z^(n-1-i)(T[b_i]) (Z: one zero byte, T: the byte table),
+// so row[k][b] = Z^k(T[b]) gives each byte's term in ONE lookup and the terms
+// XOR together in any order -- sixteen lanes look up a header byte each, where
+// a byte-table walk would be twelve dependent loads on one lane for every
+// message.  Row kRpcIdRow is the identity: the lanes that hold the hash bytes
+// (and the bytes no hash covers) pass theirs through the same lookup.
+constexpr uint32_t kRpcIdRow = 12;
+struct RpcHdrPack {
+    uint16_t row[kRpcIdRow + 1][256];
+    uint16_t c;     // Z^n(init) ^ xorout for the kind's n
+    uint16_t kind;  // kRpcRequest / kRpcResponse
+};
+MCK_HOST_DEVICE_INLINE uint32_t rpc_hdr_row(uint32_t kind, uint32_t j) {
+    return j < rpc_img_bytes(kind) ? rpc_img_bytes(kind) - 1u - rpc_img_index(kind, j) : kRpcIdRow;
+}
+// Lane j's term (j < 16): of the CRC-16 if j < rpc_img_bytes, else the wire byte itself.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_hdr_term_index(uint32_t kind, uint32_t j, uint32_t byte) {
+    return rpc_hdr_row(kind, j) * 256u + (byte & 0xFFu);
+}
+MCK_HOST_DEVICE_INLINE uint32_t rpc_hdr_term(const RpcHdrPack *pk, uint32_t kind, uint32_t j, uint32_t byte) {
+    return (&pk->row[0][0])[rpc_hdr_term_index(kind, j, byte)];
+}
+// The header's CRC-16 from the XOR of the terms of lanes j < rpc_img_bytes.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_hdr_crc(uint32_t c, uint32_t terms) { return (c ^ terms) & 0xFFFFu; }
+
+// The pack of one 16-bit model (poly in normal form, as mck_model_t has it) and kind; both bit orders.
+inline void rpc_hdr_pack_build(uint32_t poly, bool reflected, uint32_t init, uint32_t xorout, uint32_t kind, RpcHdrPack *pk) {
+    auto reflect16 = [](uint32_t v) {
+        uint32_t r = 0;
+        for (int i = 0; i < 16; i++) r |= ((v >> i) & 1u) << (15 - i);
+        return r;
+    };
+    const uint32_t rp = reflect16(poly);
+    uint16_t T[256];
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t r = reflected ? i : i << 8;
+        for (int k = 0; k < 8; k++)
+            r = reflected ? (r & 1u ? (r >> 1) ^ rp : r >> 1) : (r & 0x8000u ? (r << 1) ^ poly : r << 1) & 0xFFFFu;
+        T[i] = (uint16_t)r;
+    }
+    auto zero_byte = [&](uint32_t r) { return reflected ? (r >> 8) ^ T[r & 0xFFu] : ((r << 8) ^ T[r >> 8]) & 0xFFFFu; };
+    for (uint32_t b = 0; b < 256; b++) {
+        uint32_t r = T[b];
+        for (uint32_t k = 0; k < kRpcIdRow; k++, r = zero_byte(r)) pk->row[k][b] = (uint16_t)r;
+        pk->row[kRpcIdRow][b] = (uint16_t)b;
+    }
+    uint32_t r = reflected ? reflect16(init) : init & 0xFFFFu;
+    for (uint32_t k = 0; k < rpc_img_bytes(kind); k++) r = zero_byte(r);
+    pk->c = (uint16_t)(r ^ xorout);
+    pk->kind = (uint16_t)kind;
+}
+
+// Whether the payload bytes of a message of L bytes are hashed here: the test
+// the whole wave makes ahead of its first payload load.  Otherwise the wave
+// hashes an empty payload and no byte behind the headers is read.
+MCK_HOST_DEVICE_INLINE bool rpc_hashes_payload(uint64_t L, bool more, uint64_t pay_off) {
+    return L >= kRpcHdrBytes && !more && L >= pay_off;
+}
+// The receiver's verdict, first matching rule first.  hdr_ok, more: of a whole
+// header only; payload_ok: of a hashed payload only (L < 16 has neither).
+MCK_HOST_DEVICE_INLINE uint32_t rpc_verify_class(uint64_t L, bool hdr_ok, bool more, uint64_t pay_off, bool payload_ok) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (!hdr_ok) return kRpcHeader;
+    if (more) return kRpcDeferred;
+    if (L < pay_off) return kRpcShort;
+    return payload_ok ? kRpcOk : kRpcPayload;
+}
+// The sender's: kRpcOk = both hashes are written, kRpcDeferred = the header's
+// alone (the HG slot is seal_detached_messages'), kRpcShort = nothing.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_seal_class(uint64_t L, bool more, uint64_t pay_off) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (more) return kRpcDeferred;
+    return L < pay_off ? kRpcShort : kRpcOk;
+}
+
 // One instantiation of the batch kernels (crc32c_batch_kernel,
 // crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
 struct KernelKey {
     int width, lg, mode, op;
     bool nt, light, split;
     bool detached = false;
+    bool rpc = false;  // whole RPC messages: core header, flags and payload in one pass (the rules above)
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split && a.detached == b.detached;
+           a.split == b.split && a.detached == b.detached && a.rpc == b.rpc;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -301,6 +406,8 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
     if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
     // detached: the message verify and seal of the CRC-32C offsets kernels (light, full, non-temporal)
     if (k.detached && (k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
+    // rpc: the same six kernels' twins, in place -- never detached
+    if (k.rpc && (k.detached || k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
     if (k.split)  // pieces of aligned CRC-64 payloads, 64 lanes each: checksums only
         return k.width == 64 && k.mode == kFixedAligned && k.lg == CRC_GPU_MAX_LOG2G && k.op == kOpChecksum;
     switch (k.mode) {
@@ -323,9 +430,9 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
-inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, bool detached = false) {
-    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached};
-    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached};
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, bool detached = false, bool rpc = false) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached, rpc};
+    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached, rpc};
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;
     if (k.light || k.mode == kFixedGeneric) k.nt = false;

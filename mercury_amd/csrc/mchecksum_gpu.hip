@@ -340,11 +340,11 @@ struct KLaunch {
 };
 
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
-template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, bool DETACHED>
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, bool DETACHED, bool RPC>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED})) {
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED, RPC})) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
-        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, DETACHED>, S::block, S::blocks_per_cu};
+        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, DETACHED, RPC>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
     return {};
@@ -369,8 +369,10 @@ KLaunch kernel_for(const KernelKey &k) {
                         return lift<2>(k.light, [&](auto light) {
                             return lift<2>(k.split, [&](auto split) {
                                 return lift<2>(k.detached, [&](auto det) {
-                                    return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0, split() != 0,
-                                                      det() != 0>();
+                                    return lift<2>(k.rpc, [&](auto rpc) {
+                                        return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
+                                                          split() != 0, det() != 0, rpc() != 0>();
+                                    });
                                 });
                             });
                         });
@@ -403,19 +405,65 @@ struct OffsetsCall {
     bool detached = false;
     void *hdr = nullptr;
     const uint64_t *hdr_off = nullptr;
+    // whole RPC messages (launch_plan.h, KernelKey::rpc): src holds the messages, `out` the same bytes writable
+    // for a seal; the core header's kind and its 16-bit method; pay_off, hash_off; mismatches = the six class counts
+    bool rpc = false;
+    int kind = 0;
+    const char *hdr_method = nullptr;
 };
+
+// The header pack of a 16-bit model and kind on the device (launch_plan.h,
+// RpcHdrPack), built and uploaded once (under g_mu), then read without a lock.
+int get_rpc_pack(DevCtx *c, int idx, int kind, const void **out) {
+    if (void *p = c->rpc[idx][kind].load(std::memory_order_acquire)) {
+        *out = p;
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (void *p = c->rpc[idx][kind].load(std::memory_order_relaxed)) {
+        *out = p;
+        return 0;
+    }
+    const mck_model_t &m = mck_models[idx];
+    RpcHdrPack *host = (RpcHdrPack *)calloc(1, sizeof(RpcHdrPack));
+    if (!host) return set_err(MCHECKSUM_GPU_EINVAL, "table build failed for %s", m.name);
+    rpc_hdr_pack_build((uint32_t)m.poly, m.reflected != 0, (uint32_t)m.init, (uint32_t)m.xorout, (uint32_t)kind, host);
+    void *d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(RpcHdrPack));
+    if (e == hipSuccess) e = hipMemcpy(d, host, sizeof(RpcHdrPack), hipMemcpyHostToDevice);
+    free(host);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        return hip_err(e, "table upload");
+    }
+    c->rpc[idx][kind].store(d, std::memory_order_release);
+    *out = d;
+    return 0;
+}
+static_assert(kRpcRequest == MCHECKSUM_GPU_CORE_HEADER_REQUEST && kRpcResponse == MCHECKSUM_GPU_CORE_HEADER_RESPONSE &&
+                  kRpcOk == MCHECKSUM_GPU_RPC_OK && kRpcPayload == MCHECKSUM_GPU_RPC_PAYLOAD &&
+                  kRpcHeader == MCHECKSUM_GPU_RPC_HEADER && kRpcShort == MCHECKSUM_GPU_RPC_SHORT &&
+                  kRpcDeferred == MCHECKSUM_GPU_RPC_DEFERRED && kRpcFault == MCHECKSUM_GPU_RPC_FAULT &&
+                  kRpcClasses == MCHECKSUM_GPU_RPC_CLASSES,
+              "launch_plan.h and mchecksum_gpu.h name the kinds and classes alike");
 
 // The front of every offsets-shaped entry point: argument checks, model,
 // device context, plan, table pack, BatchArgs, slot and launch.  The calls on
 // HG messages (seal, pack, unpack) check the method ahead of the device, as an
 // argument (as verify_core_headers does); the others the device first.
 int offsets_call(const OffsetsCall &c) {
-    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal || c.detached;
+    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal || c.detached || c.rpc;
     const bool stores = c.op == kOpChecksum || c.op == kOpUpdate || (c.op == kOpSeal && !c.detached);
     // an empty batch needs no buffers (not even the one-entry offsets table)
     if (c.count && (!c.src || !c.src_off || (stores && !c.out) || (copies && (!c.dst || !c.dst_off)) ||
-                    (c.detached && (!c.hdr || !c.hdr_off)) || (c.op == kOpVerify && !c.msg && !c.detached && !c.expected)))
+                    (c.detached && (!c.hdr || !c.hdr_off)) ||
+                    (c.op == kOpVerify && !c.msg && !c.detached && !c.rpc && !c.expected)))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (c.rpc && c.kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && c.kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
+        return set_err(MCHECKSUM_GPU_EINVAL, "unknown core header kind %d", c.kind);
+    if (c.rpc && (c.hash_off < kRpcHdrBytes || c.hash_off > kMaxHashOff || c.hash_off + 4 > c.pay_off))
+        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must lie behind the core header, at most 2^30, and hash_offset + 4 "
+                                             "must not exceed payload_offset");
     if (c.msg && (c.hash_off + 4 > c.pay_off || c.pay_off > (1u << 30)))
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
     if (c.detached && c.hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
@@ -427,6 +475,15 @@ int offsets_call(const OffsetsCall &c) {
         if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
         // the detached epilogue stores and compares x ^ xorout unswapped: reflected models (both 32-bit ones are)
         if (c.detached && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no detached message kernel");
+        if (c.rpc && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no RPC message kernel");
+    }
+    int hdr_idx = -1;
+    if (c.rpc) {
+        hdr_idx = mck_model_index(c.hdr_method);
+        if (hdr_idx < 0)
+            return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", c.hdr_method ? c.hdr_method : "(null)");
+        if (mck_models[hdr_idx].width != 16)
+            return set_err(MCHECKSUM_GPU_EMETHOD, "core headers carry a 16-bit hash: \"%s\" is not a crc16 model", c.hdr_method);
     }
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
     if (!hg && (rc = resolve_model(c.method, &m))) return rc;
@@ -437,10 +494,12 @@ int offsets_call(const OffsetsCall &c) {
     // (an empty batch too resolves its method and builds its tables)
     if ((rc = get_pack(dc, m.idx, p.lg, &pack))) return rc;
     if (c.op == kOpUpdate && (rc = get_ext(dc, m.idx, &shift))) return rc;
+    const void *hdr_pack = nullptr;
+    if (c.rpc && (rc = get_rpc_pack(dc, hdr_idx, c.kind, &hdr_pack))) return rc;
     if (c.count == 0) return MCHECKSUM_GPU_OK;
     if (c.msg && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const KLaunch k = kernel_for(kernel_key(p, c.op, c.detached));
+    const KLaunch k = kernel_for(kernel_key(p, c.op, c.detached, c.rpc));
     if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     BatchArgs a{};
     a.base = (const uint8_t *)c.src;
@@ -450,7 +509,9 @@ int offsets_call(const OffsetsCall &c) {
     a.out = copies ? c.dst : c.detached ? c.hdr : c.out;
     if (copies) a.dst_offsets = c.dst_off;
     else if (c.detached) a.dst_offsets = c.hdr_off;
+    else if (c.rpc) a.expected = hdr_pack;  // (compares by header, stores no values: the pointer is free for the 16-bit model)
     else a.expected = c.expected;
+    if (c.rpc) a.len = c.pay_off;  // in 64 bits: a fixed batch's field, free in an offsets batch
     a.status = c.status;
     a.mismatches = c.mismatches;
     a.pack = pack;
@@ -917,7 +978,10 @@ int mchecksum_gpu_prepare(const char *hash_method) {
     // split CRC-64 pieces, segments, XDR; CRC-16 byte table: core headers),
     // so that no call captured into a graph uploads anything
     const void *ext = nullptr;
-    return get_ext(c, idx, &ext);
+    if ((rc = get_ext(c, idx, &ext))) return rc;
+    // ... and a 16-bit model's header packs of both kinds (the RPC message calls)
+    for (int kind = 0; mck_models[idx].width == 16 && !rc && kind < 2; kind++) rc = get_rpc_pack(c, idx, kind, &ext);
+    return rc;
 }
 
 int mchecksum_gpu_lanes_per_payload(const char *hash_method, size_t len) {
@@ -1047,6 +1111,36 @@ int mchecksum_gpu_seal_detached_messages(const char *hash_method, void *dev_msgs
     c.detached = true;
     c.hdr = dev_msgs;
     c.hdr_off = dev_msg_offsets;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_verify_rpc_messages(const char *header_method, const char *payload_method, int kind, const void *dev_buf,
+                                      const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                      size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
+    OffsetsCall c{kOpVerify, payload_method, dev_buf, dev_msg_offsets, count};
+    c.rpc = true;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_counts;  // the six class counts
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_seal_rpc_messages(const char *header_method, const char *payload_method, int kind, void *dev_buf,
+                                    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                    size_t hash_offset, uint8_t *dev_status, void *stream) {
+    OffsetsCall c{kOpSeal, payload_method, dev_buf, dev_msg_offsets, count};
+    c.rpc = true;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.out = dev_buf;
+    c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;
     c.stream = stream;

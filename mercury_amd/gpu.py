@@ -725,6 +725,84 @@ def state_seal_messages(state: torch.Tensor, msgs: torch.Tensor, msg_offsets: to
     return status
 
 
+# statuses of the RPC message calls (include/mchecksum_gpu.h, MCHECKSUM_GPU_RPC_*)
+RPC_OK, RPC_PAYLOAD, RPC_HEADER, RPC_SHORT, RPC_DEFERRED, RPC_FAULT, RPC_CLASSES = range(7)
+
+
+def _check_rpc(data, msg_offsets, offsets_host, kind: str, payload_offset: int, hash_offset: int):
+    """The messages of an RPC message call; returns (count, the kind's number)."""
+    from ._lib import CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE
+    _check_device_u8(data, "data")
+    _check_offsets(data, msg_offsets, offsets_host)
+    k = {"request": CORE_HEADER_REQUEST, "response": CORE_HEADER_RESPONSE}.get(kind)
+    if k is None:
+        raise GpuChecksumError('kind must be "request" or "response"')
+    if hash_offset < 16 or hash_offset > 1 << 30 or hash_offset + 4 > payload_offset:
+        raise GpuChecksumError("hash_offset must lie in 16..2^30 and hash_offset + 4 must not exceed payload_offset")
+    count = msg_offsets.numel() - 1
+    if count < 0:
+        raise GpuChecksumError("msg_offsets needs at least one entry")
+    return count, k
+
+
+def _rpc_status(data: torch.Tensor, count: int, status):
+    """Status of an RPC message call: None allocates (every message starts as
+    FAULT, "not vouched for"), False passes none, a tensor is used as it is."""
+    if status is None:
+        return torch.full((max(count, 0),), RPC_FAULT, dtype=torch.uint8, device=data.device)
+    return False if status is False else _sender_status(data, count, status)
+
+
+def verify_rpc_messages(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str = "request",
+                        payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                        method: str = "crc32c", stream=None, offsets_host=None, status=None, counts=None):
+    """Check whole RPC messages as Mercury does, in one launch
+    (mchecksum_gpu_verify_rpc_messages): the core header's CRC-16, then its
+    flags, then -- unless MORE_DATA says the payload is elsewhere -- the CRC of
+    data[msg_offsets[i] + payload_offset : msg_offsets[i+1]] against the
+    network-order u32 at hash_offset.  Returns (status uint8 per message: RPC_OK,
+    RPC_PAYLOAD, RPC_HEADER, RPC_SHORT, RPC_DEFERRED or RPC_FAULT; counts, int32
+    per class).  status / counts: None allocates, False leaves that output out,
+    a tensor is reused (counts are added to).  Nothing is written to `data`."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    status = _rpc_status(data, count, status)
+    if counts is None:
+        counts = torch.zeros(RPC_CLASSES, dtype=torch.int32, device=data.device)
+    elif counts is not False and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32
+                                  or not counts.is_cuda or not counts.is_contiguous() or counts.numel() < RPC_CLASSES):
+        raise GpuChecksumError("counts must be a contiguous device int32 tensor of at least RPC_CLASSES elements")
+    _same_device(data, msg_offsets=msg_offsets, status=None if status is False else status,
+                 counts=None if counts is False else counts)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_verify_rpc_messages(header_method.encode(), method.encode(), k, data.data_ptr(),
+                                                      msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                      _ptr(status), _ptr(counts), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_rpc_messages")
+    return status, counts
+
+
+def seal_rpc_messages(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str = "request",
+                      payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                      method: str = "crc32c", stream=None, offsets_host=None, status=None):
+    """Sender side of verify_rpc_messages, in place: the payload CRC
+    network-order at hash_offset and the core header's CRC-16 at 12 (request) or
+    4 (response); with MORE_DATA set, the header's CRC-16 alone (RPC_DEFERRED:
+    the HG slot is seal_detached_messages').  Returns status (uint8 per message:
+    RPC_OK, RPC_DEFERRED, RPC_SHORT = nothing written, or RPC_FAULT; False
+    passes none and returns False).  Only those 2 or 6 bytes are written."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    status = _rpc_status(data, count, status)
+    _same_device(data, msg_offsets=msg_offsets, status=None if status is False else status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_seal_rpc_messages(header_method.encode(), method.encode(), k, data.data_ptr(),
+                                                    msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                    _ptr(status), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_rpc_messages")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its

@@ -22,8 +22,9 @@ A kernel's key is read from its demangled template arguments, in either
 spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
 and crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED> (bool packs), or
 <LOG2G, MODE, OP, NT, LIGHT> and <LOG2G, MODE, OP, NT, SPLIT> (BatchOp,
-launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED> (KernelKey::detached:
-such a kernel's operation reads "verify_detached" / "seal_detached").  Exit status 1 unless the pairing is one to one and every pair
+launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED[, RPC]> (KernelKey::detached:
+such a kernel's operation reads "verify_detached" / "seal_detached"; KernelKey::rpc:
+"verify_rpc" / "seal_rpc").  Exit status 1 unless the pairing is one to one and every pair
 is equal in everything.
 """
 import hashlib
@@ -48,11 +49,13 @@ def key_of(name):
     a = [{"true": 1, "false": 0}.get(t.strip(), t.strip()) for t in m.group(2).split(",")]
     a = [int(re.sub(r"^\(.*\)", "", t)) if isinstance(t, str) else t for t in a]
     lg, mode = a[0], a[1]
-    if len(a) == 5 or (len(a) == 6 and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED]>
+    if len(a) == 5 or (len(a) in (6, 7) and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED[, RPC]]>
         op, nt, last = a[2], a[3], a[4]
         light, split = (last, 0) if width == 32 else (0, last)
-        if len(a) == 6 and a[5]:  # KernelKey::detached: the slot of a verify or a seal in another buffer
+        if len(a) >= 6 and a[5]:  # KernelKey::detached: the slot of a verify or a seal in another buffer
             return (width, lg, MODES[mode], OPS[op] + "_detached", nt, light, split)
+        if len(a) == 7 and a[6]:  # KernelKey::rpc: whole RPC messages, header and flags with the payload
+            return (width, lg, MODES[mode], OPS[op] + "_rpc", nt, light, split)
     else:  # the bool packs
         verify, nt = a[2], a[3]
         if width == 32:
