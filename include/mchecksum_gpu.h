@@ -916,6 +916,86 @@ mchecksum_gpu_seal_rpc_messages(const char *header_method,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, uint8_t *dev_status, void *stream);
 
+/* Whole RPC messages with the payload moved in the same pass: what
+ * mchecksum_gpu_unpack_messages and mchecksum_gpu_pack_messages do, under the
+ * rules of the two calls above.  A receiver that copies payloads out of a
+ * drained multi-recv buffer need not verify first and unpack afterwards (two
+ * reads of every payload, and unpack_messages reports each overflow RPC as
+ * corrupt); a sender that packs payloads behind pre-filled headers need not
+ * split its batch by flag and seal the core headers in a launch of their own.
+ *
+ * Notation.  Message i, L, `kind`, `more` (bit 0 of the flags byte AS IT SITS
+ * IN THE BUFFER: byte 10 of a request, byte 1 of a response) as above.  The
+ * other range is [t[i], t[i+1]) of dev_dst_offsets / dev_src_offsets, count + 1
+ * entries, and R its length -- a table that runs backwards gives R = 0, as it
+ * gives L = 0.  Ranges are packed or not as the caller likes.
+ *
+ * Inherited, not restated: the argument checks and their order (EINVAL, then
+ * both methods EMETHOD ahead of the device, then ENODEV; the bounds on kind,
+ * count, hash_offset and payload_offset; dev_dst / dev_src and their tables
+ * are required pointers with count > 0; count == 0 needs no buffers but passes
+ * the checks first), the two methods, and the launch, capture and fail-closed
+ * rules are verify_rpc_messages' and seal_rpc_messages'; the read padding (the
+ * side that is read must be readable to the next 16-byte boundary, the written
+ * side needs none) and the no-overlap rule between what is read and what is
+ * written are unpack_messages' and pack_messages'.  No workspace, one launch, a
+ * twin of the kernel unpack_messages / pack_messages picks for the same count.
+ * Fail closed: error word + 1, once; every status the launch cannot vouch for
+ * is MCHECKSUM_GPU_RPC_FAULT; an unpack adds `count` to
+ * dev_counts[MCHECKSUM_GPU_RPC_FAULT]; the bytes written for a FAULT message
+ * are unspecified (never outside what the rules below allow to be written).
+ * DESIGN.md 4.23 has the design and the measurements. */
+#define MCHECKSUM_GPU_COPY_RPC_MISFIT   6   /* eager, whole, but message size != payload_offset + range size */
+#define MCHECKSUM_GPU_COPY_RPC_CLASSES  7   /* words of dev_counts for the unpack call */
+
+/* Receiver.  dev_status[i] is the first rule that matches:
+ *   1. L < 16                                              -> SHORT
+ *   2. the CRC-16 of the field image differs from the hash -> HEADER
+ *   3. `more`                                              -> DEFERRED
+ *   4. L < payload_offset                                  -> SHORT
+ *   5. L != payload_offset + R                             -> MISFIT
+ *   6. the payload's CRC differs from the network-order u32 at hash_offset
+ *                                                          -> PAYLOAD
+ *   7. OK
+ * What is written does not wait for the verdicts: message i's destination
+ * range is written iff L >= 16, `more` is clear, L >= payload_offset and
+ * L == payload_offset + R, and then receives exactly the R payload bytes AS
+ * RECEIVED -- whatever rules 2 and 6 say: look at the status before the bytes,
+ * as after unpack_messages.  So a HEADER message that passes that test is
+ * copied, and one that does not is untouched.  For a DEFERRED, SHORT or MISFIT
+ * message no destination byte is written, whatever R is, and no byte behind
+ * the core header is read; a DEFERRED message's R is not looked at.  Nothing
+ * else is written: nothing before t[0], in a skipped range, or past t[count];
+ * dev_buf is never written.  dev_counts: MCHECKSUM_GPU_COPY_RPC_CLASSES words
+ * the caller zeroes, dev_counts[k] grows by the number of messages of status k.
+ * Either of dev_status and dev_counts may be NULL. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_rpc_messages(const char *header_method,
+    const char *payload_method, int kind, const void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+    uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+/* Sender: the caller has filled every header byte of dev_buf except the two
+ * hashes; the flags byte is read from dev_buf.  First rule that matches:
+ *   1. L < 16                   -> SHORT: nothing written, source range not read
+ *   2. `more`                   -> DEFERRED: the header CRC-16 alone (2 bytes);
+ *                                  source range not read, whatever R is
+ *   3. L < payload_offset       -> SHORT: nothing written
+ *   4. L != payload_offset + R  -> MISFIT: nothing written
+ *   5. OK: the R source bytes are copied to dev_buf[mo[i] + payload_offset,
+ *      mo[i+1]), their CRC is stored big-endian at hash_offset and the header
+ *      CRC-16 big-endian at 12 (request) or 4 (response)
+ * Exactly those R + 6 or 2 bytes of a message are written: no other header
+ * byte, no gap, nothing past the last message.  dev_src is never written.
+ * dev_status may be NULL. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_rpc_messages(const char *header_method,
+    const char *payload_method, int kind, const void *dev_src,
+    const uint64_t *dev_src_offsets, void *dev_buf,
+    const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
 /* XDR-mode proc checksum.  In a Mercury built with
  * MERCURY_USE_XDR (HG_HAS_XDR) the serialized buffer holds XDR -- every
  * integer big-endian and rounded up to 4 bytes, byte arrays zero-padded to a

@@ -397,16 +397,20 @@ typedef const __attribute__((address_space(1))) uint16_t *rpc_tab_t;
 // A verifying workgroup's per-class counts: LDS atomics by the owning lanes
 // (none returns a value or leaves the CU), added to the caller's six words
 // once per WORKGROUP at its end, as add_mismatches adds its one.  The batch
-// kernels' LDS has room for these 24 bytes, not for a table.
+// kernels' LDS has room for these 24 bytes, not for a table.  N: the classes
+// of the call -- the unpack twin's seven words are its own, so the verify
+// twin's LDS is what it was.
+template <uint32_t N>
 __device__ __forceinline__ uint32_t *rpc_wg_counts() {
-    __shared__ uint32_t wg_cls[mck::kRpcClasses];
+    __shared__ uint32_t wg_cls[N];
     return wg_cls;
 }
 // Every thread of the workgroup calls this, once (counters zeroed ahead of the fill's barrier).
+template <uint32_t N>
 __device__ __forceinline__ void rpc_add_counts(uint32_t *ctr) {
     __syncthreads();
-    if (threadIdx.x < mck::kRpcClasses && ctr) {
-        const uint32_t v = rpc_wg_counts()[threadIdx.x];
+    if (threadIdx.x < N && ctr) {
+        const uint32_t v = rpc_wg_counts<N>()[threadIdx.x];
         if (v) atomicAdd(&ctr[threadIdx.x], v);
     }
 }
@@ -414,6 +418,8 @@ __device__ __forceinline__ void rpc_add_counts(uint32_t *ctr) {
 // verify adds `count` to the FAULT class, and every status becomes FAULT --
 // verify's and seal's, so a stale OK or DEFERRED in the caller's buffer never
 // survives; messages hashed after the sweep overwrite theirs with the truth.
+// The copying twins' too: an unpack is a verify here (its FAULT word is the
+// same one of its seven), a pack a seal.
 template <bool VERIFY>
 __device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -430,10 +436,13 @@ __device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
 // slots lie in the eager messages, a buffer and table of their own.
 // RPC (KernelKey::rpc): a verify or a seal of whole RPC messages -- the core
 // header's CRC-16 and its flags decide with the payload's CRC what a message
-// is (launch_plan.h: rpc_verify_class, rpc_seal_class).
+// is (launch_plan.h: rpc_verify_class, rpc_seal_class).  With a copying OP
+// (mchecksum_gpu_unpack_rpc_messages, _pack_rpc_messages) the payload is also
+// stored by the payload loop, and the other range's length enters the rules
+// (rpc_copies_payload, rpc_unpack_class, rpc_pack_class).
 template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, bool DETACHED = false, bool RPC = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED, RPC}), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::kernel_key_of(32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED, RPC)), "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
@@ -465,15 +474,18 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     const uint32_t init = pk->init, xorout = pk->xorout;
     // RPC: the header model's pack rides in the `expected` pointer, which a
     // verify by header and a seal leave free (two scalar loads, here for the
-    // reason above)
+    // reason above).  The copying twins keep the destination's table there
+    // (the same union) and carry the pack in `shift`, which only an update
+    // and a split batch use.
     [[maybe_unused]] rpc_tab_t rpc_tab = nullptr;
     [[maybe_unused]] uint32_t rpc_kind = 0, rpc_c = 0;
+    constexpr uint32_t kCounts = COPY ? mck::kRpcCopyClasses : mck::kRpcClasses;  // (RPC && VERIFY: the words of LDS counts)
     if constexpr (RPC) {
-        const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(a.expected);
+        const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(COPY ? a.shift : a.expected);
         rpc_tab = (rpc_tab_t)uniform64(reinterpret_cast<uint64_t>(&hp->row[0][0]));
         rpc_kind = hp->kind;
         rpc_c = hp->c;
-        if (VERIFY && threadIdx.x < mck::kRpcClasses) rpc_wg_counts()[threadIdx.x] = 0;  // (ahead of the fill's barrier)
+        if (VERIFY && threadIdx.x < kCounts) rpc_wg_counts<kCounts>()[threadIdx.x] = 0;  // (ahead of the fill's barrier)
     }
     uint4 ring0[kRing];
     const bool pre = PRE && wave < units;
@@ -501,7 +513,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     if (MODE == kOffsets) {
         auto one = [&](uint64_t p) {
             const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
-            if constexpr (COPY && VERIFY) {
+            if constexpr (COPY && VERIFY && !RPC) {
                 const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
                 // a message that does not fit its destination (one shorter than its
                 // headers never does) is hashed and copied as an empty payload
@@ -519,7 +531,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                     nbad += bad;
                 }
                 return;
-            } else if constexpr (COPY) {
+            } else if constexpr (COPY && !RPC) {
                 const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
                 // a payload that does not fit its message is hashed and copied as an empty one
                 const bool misfit = d1 - d0 != a.pay_off + (m1 - m0);
@@ -546,16 +558,48 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 // whole wave whether the payload is hashed -- ahead of the first
                 // payload load; otherwise the wave hashes an empty payload.
                 // `len` (a fixed batch's field) carries payload_offset in 64 bits.
-                const uint64_t L = mck::rpc_len(m0, m1), pay = a.len;
+                //
+                // The copying twins: the message is [g0, g0 + L) of `mbuf`, and
+                // R the length of the other range.  An unpack's message is the
+                // batch's own (base, offsets) and its destination `out` by
+                // dst_offsets; a pack's message is the WRITTEN side (out,
+                // dst_offsets: the caller filled its header, and no byte the
+                // sixteen lanes use is stored by this launch), its payload the
+                // batch's.  rpc_copies_payload decides, as above, ahead of the
+                // first payload load or store: a message that is not copied
+                // runs the empty payload, and R is not looked at with MORE_DATA.
+                const uint64_t pay = a.len;
+                uint64_t g0 = m0, g1 = m1;
+                const uint8_t *mbuf = a.base;
+                if constexpr (COPY && SEAL) {
+                    g0 = a.dst_offsets[p], g1 = a.dst_offsets[p + 1];
+                    mbuf = reinterpret_cast<const uint8_t *>(a.out);
+                }
+                const uint64_t L = mck::rpc_len(g0, g1);
                 const bool whole = L >= mck::kRpcHdrBytes;
                 uint32_t hb = 0, term = 0;
-                if (whole && lane < mck::kRpcHdrBytes) hb = global_ptr(a.base + m0, true)[lane];
+                if (whole && lane < mck::kRpcHdrBytes) hb = global_ptr(mbuf + g0, true)[lane];
                 const bool more = whole && (__builtin_amdgcn_readlane(hb, mck::rpc_flags_at(rpc_kind)) & 1u);
                 if (whole && lane < mck::kRpcHdrBytes) term = rpc_tab[mck::rpc_hdr_term_index(rpc_kind, lane, hb)];
-                const bool hashed = mck::rpc_hashes_payload(L, more, pay);
-                const uint64_t o = hashed ? m0 + pay : m0 + L, n = m0 + L - o;
-                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
-                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
+                [[maybe_unused]] uint64_t R = 0;
+                if constexpr (COPY && SEAL) R = mck::rpc_len(m0, m1);
+                else if constexpr (COPY) R = mck::rpc_len(a.dst_offsets[p], a.dst_offsets[p + 1]);
+                bool hashed;
+                if constexpr (COPY) hashed = mck::rpc_copies_payload(L, more, pay, R);
+                else hashed = mck::rpc_hashes_payload(L, more, pay);
+                uint32_t x;
+                if constexpr (COPY) {
+                    // (an unpack reads [m0 + pay, m0 + L), a pack [m0, m0 + R): R bytes either way)
+                    const uint64_t o = SEAL ? m0 : m0 + pay, n = hashed ? R : 0;
+                    uint8_t *dst = reinterpret_cast<uint8_t *>(a.out) + (SEAL ? g0 + pay : a.dst_offsets[p]);
+                    x = n < (1ull << 31)
+                            ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, dst)
+                            : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, dst);
+                } else {
+                    const uint64_t o = hashed ? m0 + pay : m0 + L, n = m0 + L - o;
+                    x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
+                                         : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
+                }
                 // the image's terms XOR over the lanes that hold them; the wire hash is two identity terms
                 uint32_t t = lane < mck::rpc_img_bytes(rpc_kind) ? term : 0u;
 #pragma unroll
@@ -566,19 +610,25 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 if (gl == 0) {
                     if constexpr (SEAL) {
                         // (byte stores: the 2 or 6 bytes share their granules with other fields and messages)
-                        uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + m0;
-                        const uint32_t cls = mck::rpc_seal_class(L, more, pay);
+                        // (a pack's payload bytes are in place by now: R + 6 or 2 bytes of a message, no others)
+                        uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + g0;
+                        uint32_t cls;
+                        if constexpr (COPY) cls = mck::rpc_pack_class(L, more, pay, R);
+                        else cls = mck::rpc_seal_class(L, more, pay);
                         if (cls == mck::kRpcOk) store_be32(msg + a.hash_off, x ^ xorout);
-                        if (cls != mck::kRpcShort) {
+                        if (COPY ? cls == mck::kRpcOk || cls == mck::kRpcDeferred : cls != mck::kRpcShort) {
                             msg[hat] = (uint8_t)(crc16 >> 8);
                             msg[hat + 1] = (uint8_t)crc16;
                         }
                         if (a.status) a.status[p] = (uint8_t)cls;
                     } else {
+                        // (an unpack's bytes are stored as received: both verdicts are known only after the copy)
                         const bool pay_ok = hashed && load_be32(a.base + m0 + a.hash_off) == (x ^ xorout);
-                        const uint32_t cls = mck::rpc_verify_class(L, crc16 == wire, more, pay, pay_ok);
+                        uint32_t cls;
+                        if constexpr (COPY) cls = mck::rpc_unpack_class(L, crc16 == wire, more, pay, R, pay_ok);
+                        else cls = mck::rpc_verify_class(L, crc16 == wire, more, pay, pay_ok);
                         if (a.status) a.status[p] = (uint8_t)cls;
-                        atomicAdd(&rpc_wg_counts()[cls], 1u);  // LDS; the device's counters once per workgroup
+                        atomicAdd(&rpc_wg_counts<kCounts>()[cls], 1u);  // LDS; the device's counters once per workgroup
                     }
                 }
                 return;
@@ -650,7 +700,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
             wave_range(a.offsets, a.count, wave, nw, &first, &last);
             for (uint64_t p = first; p < last; p++) one(p);
         }
-        if constexpr (RPC && VERIFY) rpc_add_counts(a.mismatches);
+        if constexpr (RPC && VERIFY) rpc_add_counts<kCounts>(a.mismatches);
         else if constexpr (VERIFY) add_mismatches(a.mismatches, nbad);
         MCK_STAMP(wave, 2);
         return;

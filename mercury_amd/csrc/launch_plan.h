@@ -282,7 +282,8 @@ MCK_HOST_DEVICE_INLINE uint64_t msg_slot_at(uint64_t m0, uint64_t hash_off) { re
 // hash_offset is carried in 32 bits (BatchArgs::hash_off), capped as payload_offset is
 constexpr uint64_t kMaxHashOff = 1ull << 30;
 
-// ---- whole RPC messages: mchecksum_gpu_verify_rpc_messages, _seal_rpc_messages ----
+// ---- whole RPC messages: mchecksum_gpu_verify_rpc_messages, _seal_rpc_messages,
+// ---- and with the payload copied: _unpack_rpc_messages, _pack_rpc_messages ----
 //
 // A message is a 16-byte core header (src/mercury_core_header.c:175-289), the
 // HG header with the payload hash at hash_off, and from pay_off the payload.
@@ -295,6 +296,9 @@ constexpr uint64_t kRpcHdrBytes = 16;
 // (MCHECKSUM_GPU_CORE_HEADER_REQUEST / _RESPONSE and MCHECKSUM_GPU_RPC_*; mchecksum_gpu.hip asserts they agree)
 constexpr uint32_t kRpcRequest = 0, kRpcResponse = 1;
 enum RpcClass : uint32_t { kRpcOk = 0, kRpcPayload, kRpcHeader, kRpcShort, kRpcDeferred, kRpcFault, kRpcClasses };
+// The copying calls' seventh verdict (MCHECKSUM_GPU_COPY_RPC_MISFIT, _CLASSES): eager and whole, but the message
+// is not pay_off + the other range's bytes.  Constants of their own: verify and seal keep their six classes.
+constexpr uint32_t kRpcMisfit = 6, kRpcCopyClasses = 7;
 
 // A table that runs backwards holds an empty message.
 MCK_HOST_DEVICE_INLINE uint64_t rpc_len(uint64_t m0, uint64_t m1) { return m1 >= m0 ? m1 - m0 : 0; }
@@ -386,6 +390,35 @@ MCK_HOST_DEVICE_INLINE uint32_t rpc_seal_class(uint64_t L, bool more, uint64_t p
     return L < pay_off ? kRpcShort : kRpcOk;
 }
 
+// The copying twins (kOpUnpack, kOpPack with KernelKey::rpc).  R is the length
+// of the other range -- the destination's of an unpack, the source's of a pack
+// (rpc_len of its table entries: backwards is empty).  Whether the payload is
+// copied and hashed: the whole wave's test ahead of its first payload load or
+// store.  Otherwise it copies and hashes an empty payload: no byte behind the
+// core header is read, none of the other range is read or written, and R is
+// not looked at when `more` is set.  The header's verdict does not enter.
+MCK_HOST_DEVICE_INLINE bool rpc_copies_payload(uint64_t L, bool more, uint64_t pay_off, uint64_t R) {
+    return rpc_hashes_payload(L, more, pay_off) && L - pay_off == R;
+}
+// The receiver's verdict, first matching rule first.  payload_ok: of a copied payload only.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_unpack_class(uint64_t L, bool hdr_ok, bool more, uint64_t pay_off, uint64_t R,
+                                                 bool payload_ok) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (!hdr_ok) return kRpcHeader;
+    if (more) return kRpcDeferred;
+    if (L < pay_off) return kRpcShort;
+    if (L - pay_off != R) return kRpcMisfit;
+    return payload_ok ? kRpcOk : kRpcPayload;
+}
+// The sender's: kRpcOk = the payload and both hashes are written, kRpcDeferred
+// = the header's hash alone, kRpcShort and kRpcMisfit = nothing.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_pack_class(uint64_t L, bool more, uint64_t pay_off, uint64_t R) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (more) return kRpcDeferred;
+    if (L < pay_off) return kRpcShort;
+    return L - pay_off != R ? kRpcMisfit : kRpcOk;
+}
+
 // One instantiation of the batch kernels (crc32c_batch_kernel,
 // crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
 struct KernelKey {
@@ -393,10 +426,13 @@ struct KernelKey {
     bool nt, light, split;
     bool detached = false;
     bool rpc = false;  // whole RPC messages: core header, flags and payload in one pass (the rules above)
+    // ... with the payload moved in the same pass (kOpUnpack, kOpPack): a field of its own, never set with
+    // `rpc`, so the keys `rpc` names stay the six verify and seal twins.  Both are the kernels' RPC argument.
+    bool rpc_copy = false;
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split && a.detached == b.detached && a.rpc == b.rpc;
+           a.split == b.split && a.detached == b.detached && a.rpc == b.rpc && a.rpc_copy == b.rpc_copy;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -408,6 +444,9 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
     if (k.detached && (k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
     // rpc: the same six kernels' twins, in place -- never detached
     if (k.rpc && (k.detached || k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
+    // rpc_copy: the twins of the six copying kernels (pack and unpack: light, full, non-temporal)
+    if (k.rpc_copy && (k.rpc || k.detached || k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpPack && k.op != kOpUnpack)))
+        return false;
     if (k.split)  // pieces of aligned CRC-64 payloads, 64 lanes each: checksums only
         return k.width == 64 && k.mode == kFixedAligned && k.lg == CRC_GPU_MAX_LOG2G && k.op == kOpChecksum;
     switch (k.mode) {
@@ -430,9 +469,16 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
+// The key of a kernel's template arguments.  rpc (the kernels' RPC argument):
+// whole RPC messages -- KernelKey::rpc, or ::rpc_copy for an op that copies.
+constexpr KernelKey kernel_key_of(int width, int lg, int mode, int op, bool nt, bool light, bool split, bool detached, bool rpc) {
+    const bool copy = rpc && (op == kOpPack || op == kOpUnpack);
+    return KernelKey{width, lg, mode, op, nt, light, split, detached, rpc && !copy, copy};
+}
+
 inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, bool detached = false, bool rpc = false) {
-    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached, rpc};
-    if (p.split) k = KernelKey{64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached, rpc};
+    KernelKey k = kernel_key_of(p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached, rpc);
+    if (p.split) k = kernel_key_of(64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached, rpc);
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;
     if (k.light || k.mode == kFixedGeneric) k.nt = false;

@@ -342,7 +342,7 @@ struct KLaunch {
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
 template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, bool DETACHED, bool RPC>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED, RPC})) {
+    if constexpr (kernel_key_valid(kernel_key_of(W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED, RPC))) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
         if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, DETACHED, RPC>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
@@ -359,8 +359,10 @@ KLaunch lift(int x, const F &f) {
 
 // The kernel of a key (launch_plan.h: kernel_key): each field becomes a
 // template argument in turn.  A key with no kernel gives a null KLaunch, which
-// the callers report as an error and never launch.
+// the callers report as an error and never launch.  The kernels' RPC argument
+// is the key's rpc or rpc_copy (kernel_key_of: the operation says which).
 KLaunch kernel_for(const KernelKey &k) {
+    if (!kernel_key_valid(k)) return {};
     return lift<2>(k.width == 32 ? 0 : k.width == 64 ? 1 : -1, [&](auto w64) {
         return lift<CRC_GPU_MAX_LOG2G + 1>(k.lg, [&](auto lg) {
             return lift<kOffsets + 1>(k.mode, [&](auto mode) {
@@ -369,7 +371,7 @@ KLaunch kernel_for(const KernelKey &k) {
                         return lift<2>(k.light, [&](auto light) {
                             return lift<2>(k.split, [&](auto split) {
                                 return lift<2>(k.detached, [&](auto det) {
-                                    return lift<2>(k.rpc, [&](auto rpc) {
+                                    return lift<2>(k.rpc || k.rpc_copy, [&](auto rpc) {
                                         return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
                                                           split() != 0, det() != 0, rpc() != 0>();
                                     });
@@ -406,7 +408,9 @@ struct OffsetsCall {
     void *hdr = nullptr;
     const uint64_t *hdr_off = nullptr;
     // whole RPC messages (launch_plan.h, KernelKey::rpc): src holds the messages, `out` the same bytes writable
-    // for a seal; the core header's kind and its 16-bit method; pay_off, hash_off; mismatches = the six class counts
+    // for a seal; the core header's kind and its 16-bit method; pay_off, hash_off; mismatches = the six class counts.
+    // With kOpUnpack / kOpPack (the copying twins) the two buffers and tables are pack's and unpack's -- an unpack's
+    // messages at src, a pack's at dst --, `msg` stays clear, and mismatches = the seven class counts of an unpack
     bool rpc = false;
     int kind = 0;
     const char *hdr_method = nullptr;
@@ -444,7 +448,8 @@ static_assert(kRpcRequest == MCHECKSUM_GPU_CORE_HEADER_REQUEST && kRpcResponse =
                   kRpcOk == MCHECKSUM_GPU_RPC_OK && kRpcPayload == MCHECKSUM_GPU_RPC_PAYLOAD &&
                   kRpcHeader == MCHECKSUM_GPU_RPC_HEADER && kRpcShort == MCHECKSUM_GPU_RPC_SHORT &&
                   kRpcDeferred == MCHECKSUM_GPU_RPC_DEFERRED && kRpcFault == MCHECKSUM_GPU_RPC_FAULT &&
-                  kRpcClasses == MCHECKSUM_GPU_RPC_CLASSES,
+                  kRpcClasses == MCHECKSUM_GPU_RPC_CLASSES && kRpcMisfit == MCHECKSUM_GPU_COPY_RPC_MISFIT &&
+                  kRpcCopyClasses == MCHECKSUM_GPU_COPY_RPC_CLASSES,
               "launch_plan.h and mchecksum_gpu.h name the kinds and classes alike");
 
 // The front of every offsets-shaped entry point: argument checks, model,
@@ -521,6 +526,7 @@ int offsets_call(const OffsetsCall &c) {
     a.err_word = error_word();
     a.bswap = c.op == kOpVerify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
     a.shift = shift;
+    if (c.rpc && copies) a.shift = hdr_pack;  // (`expected` is the destination's table here; no update, no split: free)
     SlotRef sr;
     if (p.dyn) sr = queue_slot(dc, c.stream);
     a.queue = sr.q;
@@ -1140,6 +1146,43 @@ int mchecksum_gpu_seal_rpc_messages(const char *header_method, const char *paylo
     c.kind = kind;
     c.hdr_method = header_method;
     c.out = dev_buf;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_unpack_rpc_messages(const char *header_method, const char *payload_method, int kind, const void *dev_buf,
+                                      const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                      size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+                                      uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
+    // unpack_messages' buffers under verify_rpc_messages' rules: the messages are the source
+    OffsetsCall c{kOpUnpack, payload_method, dev_buf, dev_msg_offsets, count};
+    c.rpc = true;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.dst = dev_dst;
+    c.dst_off = dev_dst_offsets;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_counts;  // the seven class counts
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_pack_rpc_messages(const char *header_method, const char *payload_method, int kind, const void *dev_src,
+                                    const uint64_t *dev_src_offsets, void *dev_buf, const uint64_t *dev_msg_offsets,
+                                    size_t count, size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+                                    void *stream) {
+    // pack_messages' buffers under seal_rpc_messages' rules: the headers (and their flags) are read from dev_buf
+    OffsetsCall c{kOpPack, payload_method, dev_src, dev_src_offsets, count};
+    c.rpc = true;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.dst = dev_buf;
+    c.dst_off = dev_msg_offsets;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;

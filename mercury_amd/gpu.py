@@ -803,6 +803,92 @@ def seal_rpc_messages(data: torch.Tensor, msg_offsets: torch.Tensor, kind: str =
     return status
 
 
+# the copying RPC calls' seventh status and their count words (MCHECKSUM_GPU_COPY_RPC_MISFIT, _CLASSES)
+RPC_MISFIT, RPC_COPY_CLASSES = 6, 7
+
+
+def _check_rpc_copy(data, msg_offsets, offsets_host, other, other_offsets, other_host, names):
+    """The second buffer and table of a copying RPC call.  With both host
+    tables, the two ranges must not overlap; the fit rule is not raised on:
+    RPC_MISFIT is a verdict of these calls."""
+    _check_device_u8(other, names[0])
+    _check_offsets(other, other_offsets, other_host)
+    count = msg_offsets.numel() - 1
+    if other_offsets.numel() != count + 1:
+        raise GpuChecksumError(f"msg_offsets and {names[1]} need the same number (>= 1) of entries")
+    if offsets_host is not None and other_host is not None and count:
+        import numpy as np
+        mo, oo = np.asarray(offsets_host, dtype=np.uint64), np.asarray(other_host, dtype=np.uint64)
+        m0, o0 = data.data_ptr() + int(mo[0]), other.data_ptr() + int(oo[0])
+        if m0 < o0 + int(oo[-1] - oo[0]) and o0 < m0 + int(mo[-1] - mo[0]):
+            raise GpuChecksumError(f"the message and {names[0]} ranges overlap")
+
+
+def unpack_rpc_messages(data: torch.Tensor, msg_offsets: torch.Tensor, dst: torch.Tensor, dst_offsets: torch.Tensor,
+                        kind: str = "request", payload_offset: int = 20, hash_offset: int = 16,
+                        header_method: str = "crc16", method: str = "crc32c", stream=None, offsets_host=None,
+                        dst_offsets_host=None, status=None, counts=None):
+    """verify_rpc_messages that also copies the payloads out, in one launch
+    (mchecksum_gpu_unpack_rpc_messages): the payload of an eager, whole message
+    whose size is payload_offset + its destination's goes to
+    dst[dst_offsets[i] : dst_offsets[i+1]] as received -- whatever the header's
+    and the payload's CRC turn out to be; look at the status first.  Returns
+    (status uint8 per message: RPC_OK, RPC_PAYLOAD, RPC_HEADER, RPC_SHORT,
+    RPC_DEFERRED, RPC_MISFIT or RPC_FAULT; counts, int32 per class,
+    RPC_COPY_CLASSES words).  Nothing of a DEFERRED, SHORT or MISFIT message's
+    destination is written.  status / counts as for verify_rpc_messages.  `data`
+    and `dst` must not overlap; with both host tables given that is checked
+    here (the fit is not: a misfit is a verdict)."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    _check_rpc_copy(data, msg_offsets, offsets_host, dst, dst_offsets, dst_offsets_host, ("dst", "dst_offsets"))
+    status = _rpc_status(data, count, status)
+    if counts is None:
+        counts = torch.zeros(RPC_COPY_CLASSES, dtype=torch.int32, device=data.device)
+    elif counts is not False and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32
+                                  or not counts.is_cuda or not counts.is_contiguous()
+                                  or counts.numel() < RPC_COPY_CLASSES):
+        raise GpuChecksumError("counts must be a contiguous device int32 tensor of at least RPC_COPY_CLASSES elements")
+    _same_device(data, msg_offsets=msg_offsets, dst=dst, dst_offsets=dst_offsets,
+                 status=None if status is False else status, counts=None if counts is False else counts)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_unpack_rpc_messages(header_method.encode(), method.encode(), k, data.data_ptr(),
+                                                      msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                      dst.data_ptr(), dst_offsets.data_ptr(), _ptr(status),
+                                                      _ptr(counts), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_rpc_messages")
+    return status, counts
+
+
+def pack_rpc_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: torch.Tensor, msg_offsets: torch.Tensor,
+                      kind: str = "request", payload_offset: int = 20, hash_offset: int = 16,
+                      header_method: str = "crc16", method: str = "crc32c", stream=None, src_offsets_host=None,
+                      offsets_host=None, status=None):
+    """seal_rpc_messages that also copies the payloads in, in one launch
+    (mchecksum_gpu_pack_rpc_messages): the caller has filled every header byte
+    of `data` but the two hashes.  An eager, whole message whose size is
+    payload_offset + its source's gets src[src_offsets[i] : src_offsets[i+1]]
+    behind its headers, the payload CRC at hash_offset and the core header's
+    CRC-16 (RPC_OK); one with MORE_DATA set the header's CRC-16 alone
+    (RPC_DEFERRED, its source range is not read); RPC_SHORT and RPC_MISFIT
+    messages are not written.  Returns status (uint8 per message, or RPC_FAULT;
+    False passes none and returns False).  `src` and `data` must not overlap;
+    with both host tables given that is checked here (the fit is not)."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    _check_rpc_copy(data, msg_offsets, offsets_host, src, src_offsets, src_offsets_host, ("src", "src_offsets"))
+    status = _rpc_status(data, count, status)
+    _same_device(data, src=src, src_offsets=src_offsets, msg_offsets=msg_offsets,
+                 status=None if status is False else status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_pack_rpc_messages(header_method.encode(), method.encode(), k, src.data_ptr(),
+                                                    src_offsets.data_ptr(), data.data_ptr(), msg_offsets.data_ptr(),
+                                                    count, payload_offset, hash_offset, _ptr(status),
+                                                    _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_rpc_messages")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its

@@ -24,7 +24,7 @@ and crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED> (bool packs), or
 <LOG2G, MODE, OP, NT, LIGHT> and <LOG2G, MODE, OP, NT, SPLIT> (BatchOp,
 launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED[, RPC]> (KernelKey::detached:
 such a kernel's operation reads "verify_detached" / "seal_detached"; KernelKey::rpc:
-"verify_rpc" / "seal_rpc").  Exit status 1 unless the pairing is one to one and every pair
+"verify_rpc" / "seal_rpc", and "pack_rpc" / "unpack_rpc" for the copying twins).  Exit status 1 unless the pairing is one to one and every pair
 is equal in everything.
 """
 import hashlib
