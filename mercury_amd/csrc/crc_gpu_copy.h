@@ -35,6 +35,10 @@ struct CopyArgs {
     uint8_t *dst;
     const uint64_t *dst_starts;  // count byte offsets into dst
 };
+MCK_AT(CopyArgs, b, 0);
+MCK_AT(CopyArgs, dst, 136);
+MCK_AT(CopyArgs, dst_starts, 144);
+static_assert(sizeof(CopyArgs) == 152, "CopyArgs changed size");
 
 // OP (copy_plan.h, CopyOp): what the owning lane does with a chunk's CRC.
 template <int OP, bool NT, bool LIGHT>

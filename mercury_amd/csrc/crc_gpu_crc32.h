@@ -390,7 +390,7 @@ __device__ __forceinline__ uint32_t payload32_g64(TAB lds, const crc32_gpu_pack_
 template <bool LIGHT>
 constexpr int kBlk32 = LIGHT ? kLightBlock : kBlock;
 
-// ---- whole RPC messages (KernelKey::rpc) ----
+// ---- whole RPC messages (kFrameRpc) ----
 // The header pack's rows through a global pointer (a flat load would also count against the LDS waits).
 typedef const __attribute__((address_space(1))) uint16_t *rpc_tab_t;
 
@@ -432,23 +432,24 @@ __device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
 }
 
 // OP (launch_plan.h, BatchOp): what the owning lane does with a payload's CRC.
-// DETACHED (launch_plan.h, KernelKey::detached): a verify's or a seal's hash
-// slots lie in the eager messages, a buffer and table of their own.
-// RPC (KernelKey::rpc): a verify or a seal of whole RPC messages -- the core
-// header's CRC-16 and its flags decide with the payload's CRC what a message
-// is (launch_plan.h: rpc_verify_class, rpc_seal_class).  With a copying OP
-// (mchecksum_gpu_unpack_rpc_messages, _pack_rpc_messages) the payload is also
-// stored by the payload loop, and the other range's length enters the rules
-// (rpc_copies_payload, rpc_unpack_class, rpc_pack_class).
-template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, bool DETACHED = false, bool RPC = false>
+// FRAME (launch_plan.h, MsgFrame): what surrounds a payload and where its hash
+// slot is.  kFrameDetached: a verify's or a seal's slots lie in the eager
+// messages, a buffer and table of their own.  kFrameRpc: whole RPC messages --
+// the core header's CRC-16 and its flags decide with the payload's CRC what a
+// message is (launch_plan.h: rpc_verify_class, rpc_seal_class); with a copying
+// OP the payload is also stored by the payload loop, and the other range's
+// length enters the rules (rpc_copies_payload, rpc_unpack_class,
+// rpc_pack_class).  In place is the payloads frame's kernels (BatchArgs::msg).
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, mck::MsgFrame FRAME = mck::kFramePayloads>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::kernel_key_of(32, LOG2G, MODE, OP, NT, LIGHT, false, DETACHED, RPC)), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, FRAME}), "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
         SEED = OP == mck::kOpUpdate,
         SEAL = OP == mck::kOpSeal || OP == mck::kOpPack,
-        COPY = OP == mck::kOpPack || OP == mck::kOpUnpack
+        COPY = OP == mck::kOpPack || OP == mck::kOpUnpack,
+        RPC = FRAME == mck::kFrameRpc
     };
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
@@ -472,16 +473,12 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     // barrier they became a vector load per payload whose wait, merged with
     // the ring's at the prefetch branch, cost a vmcnt(0) per payload)
     const uint32_t init = pk->init, xorout = pk->xorout;
-    // RPC: the header model's pack rides in the `expected` pointer, which a
-    // verify by header and a seal leave free (two scalar loads, here for the
-    // reason above).  The copying twins keep the destination's table there
-    // (the same union) and carry the pack in `shift`, which only an update
-    // and a split batch use.
+    // RPC: the header model's pack (two scalar loads, here for the reason above)
     [[maybe_unused]] rpc_tab_t rpc_tab = nullptr;
     [[maybe_unused]] uint32_t rpc_kind = 0, rpc_c = 0;
     constexpr uint32_t kCounts = COPY ? mck::kRpcCopyClasses : mck::kRpcClasses;  // (RPC && VERIFY: the words of LDS counts)
     if constexpr (RPC) {
-        const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(COPY ? a.shift : a.expected);
+        const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(COPY ? a.rpc_copy_hdr_pack : a.rpc_hdr_pack);
         rpc_tab = (rpc_tab_t)uniform64(reinterpret_cast<uint64_t>(&hp->row[0][0]));
         rpc_kind = hp->kind;
         rpc_c = hp->c;
@@ -513,43 +510,6 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
     if (MODE == kOffsets) {
         auto one = [&](uint64_t p) {
             const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
-            if constexpr (COPY && VERIFY && !RPC) {
-                const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
-                // a message that does not fit its destination (one shorter than its
-                // headers never does) is hashed and copied as an empty payload
-                const bool misfit = m1 - m0 != a.pay_off + (d1 - d0);
-                const uint64_t o = misfit ? m1 : m0 + a.pay_off, n = m1 - o;
-                uint8_t *dst = reinterpret_cast<uint8_t *>(a.out) + d0;
-                const uint32_t x =
-                    n < (1ull << 31)
-                        ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, dst)
-                        : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, dst);
-                if (gl == 0) {
-                    // (the bytes are stored as received: the value is known only after the copy)
-                    const bool bad = misfit || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
-                    if (a.status) a.status[p] = bad ? 1 : 0;
-                    nbad += bad;
-                }
-                return;
-            } else if constexpr (COPY && !RPC) {
-                const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
-                // a payload that does not fit its message is hashed and copied as an empty one
-                const bool misfit = d1 - d0 != a.pay_off + (m1 - m0);
-                const uint64_t o = misfit ? m1 : m0, n = m1 - o;
-                uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + d0;
-                const uint32_t x =
-                    n < (1ull << 31)
-                        ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, msg + a.pay_off)
-                        : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, msg + a.pay_off);
-                if (gl == 0) {
-                    // (the hash slot's neighbours in its 16-byte granule are
-                    // other messages' payload and header bytes: byte stores
-                    // here, and whole-piece stores only inside a payload)
-                    if (!misfit) store_be32(msg + a.hash_off, x ^ xorout);
-                    if (a.status) a.status[p] = misfit ? 1 : 0;
-                }
-                return;
-            }
             if constexpr (RPC) {
                 // A whole RPC message.  Lanes 0..15 load a header byte each and
                 // look up its term of the CRC-16 (launch_plan.h, RpcHdrPack:
@@ -557,23 +517,22 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 // The flags byte, from its lane, and the length decide for the
                 // whole wave whether the payload is hashed -- ahead of the first
                 // payload load; otherwise the wave hashes an empty payload.
-                // `len` (a fixed batch's field) carries payload_offset in 64 bits.
                 //
                 // The copying twins: the message is [g0, g0 + L) of `mbuf`, and
                 // R the length of the other range.  An unpack's message is the
-                // batch's own (base, offsets) and its destination `out` by
-                // dst_offsets; a pack's message is the WRITTEN side (out,
+                // batch's own (base, offsets) and its destination copy_dst by
+                // dst_offsets; a pack's message is the WRITTEN side (msgs,
                 // dst_offsets: the caller filled its header, and no byte the
                 // sixteen lanes use is stored by this launch), its payload the
                 // batch's.  rpc_copies_payload decides, as above, ahead of the
                 // first payload load or store: a message that is not copied
                 // runs the empty payload, and R is not looked at with MORE_DATA.
-                const uint64_t pay = a.len;
+                const uint64_t pay = a.rpc_pay_off();
                 uint64_t g0 = m0, g1 = m1;
                 const uint8_t *mbuf = a.base;
                 if constexpr (COPY && SEAL) {
                     g0 = a.dst_offsets[p], g1 = a.dst_offsets[p + 1];
-                    mbuf = reinterpret_cast<const uint8_t *>(a.out);
+                    mbuf = a.msgs;
                 }
                 const uint64_t L = mck::rpc_len(g0, g1);
                 const bool whole = L >= mck::kRpcHdrBytes;
@@ -591,7 +550,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 if constexpr (COPY) {
                     // (an unpack reads [m0 + pay, m0 + L), a pack [m0, m0 + R): R bytes either way)
                     const uint64_t o = SEAL ? m0 : m0 + pay, n = hashed ? R : 0;
-                    uint8_t *dst = reinterpret_cast<uint8_t *>(a.out) + (SEAL ? g0 + pay : a.dst_offsets[p]);
+                    uint8_t *dst = a.copy_dst + (SEAL ? g0 + pay : a.dst_offsets[p]);
                     x = n < (1ull << 31)
                             ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, dst)
                             : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, dst);
@@ -611,7 +570,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                     if constexpr (SEAL) {
                         // (byte stores: the 2 or 6 bytes share their granules with other fields and messages)
                         // (a pack's payload bytes are in place by now: R + 6 or 2 bytes of a message, no others)
-                        uint8_t *msg = reinterpret_cast<uint8_t *>(a.out) + g0;
+                        uint8_t *msg = a.msgs + g0;
                         uint32_t cls;
                         if constexpr (COPY) cls = mck::rpc_pack_class(L, more, pay, R);
                         else cls = mck::rpc_seal_class(L, more, pay);
@@ -631,20 +590,18 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                         atomicAdd(&rpc_wg_counts<kCounts>()[cls], 1u);  // LDS; the device's counters once per workgroup
                     }
                 }
-                return;
-            }
-            if constexpr (DETACHED) {
+            } else if constexpr (FRAME == mck::kFrameDetached) {
                 // The payload is the whole of [m0, m1); its hash slot is in eager
-                // message p of another buffer (`out`, by the table dst_offsets),
+                // message p of another buffer (msgs, by the table dst_offsets),
                 // four bytes at any alignment -- the in-place epilogues below at
                 // another address (launch_plan.h: msg_slot_ok, msg_slot_at).  A
-                // verify reads `out` only.
+                // verify reads msgs only.
                 const uint64_t h0 = a.dst_offsets[p], h1 = a.dst_offsets[p + 1], n = m1 - m0;
                 const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + m0, n, gl, lc0, lc1)
                                                     : payload32_generic<LOG2G, NT>(lds, pk, a.base + m0, n, gl, lc0, lc1);
                 if (gl == 0) {
                     const bool short_msg = !mck::msg_slot_ok(h0, h1, a.hash_off);
-                    uint8_t *slot = reinterpret_cast<uint8_t *>(a.out) + mck::msg_slot_at(h0, a.hash_off);
+                    uint8_t *slot = a.msgs + mck::msg_slot_at(h0, a.hash_off);
                     if constexpr (SEAL) {
                         if (!short_msg) store_be32(slot, x ^ xorout);
                         if (a.status) a.status[p] = short_msg ? 1 : 0;
@@ -654,38 +611,67 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                         nbad += bad;
                     }
                 }
-                return;
-            }
-            // message mode: a message shorter than its headers fails verification
-            const bool short_msg = a.msg && m1 - m0 < a.pay_off;
-            const uint64_t o = a.msg ? (short_msg ? m1 : m0 + a.pay_off) : m0;
-            const uint64_t n = m1 - o;
-            const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
-                                                : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
-            if constexpr (SEED) {
+            } else if constexpr (COPY) {
+                // In place, the payload moved.  The message is the side with the
+                // headers -- an unpack's source, a pack's destination --, L bytes,
+                // and R the other range's.  A pair that does not fit (a message
+                // shorter than its headers never does) is hashed and copied as an
+                // empty payload: status 1, no byte written, and an unpack's mismatch.
+                const uint64_t d0 = a.dst_offsets[p], d1 = a.dst_offsets[p + 1];
+                const uint64_t L = SEAL ? d1 - d0 : m1 - m0, R = SEAL ? m1 - m0 : d1 - d0;
+                const bool misfit = L != a.pay_off + R;
+                const uint64_t o = misfit ? m1 : SEAL ? m0 : m0 + a.pay_off, n = m1 - o;
+                uint8_t *dst = a.copy_dst + d0;  // (a pack's is its message: the payload goes behind the headers)
+                const uint32_t x =
+                    n < (1ull << 31)
+                        ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, SEAL ? dst + a.pay_off : dst)
+                        : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, SEAL ? dst + a.pay_off : dst);
                 if (gl == 0) {
-                    uint32_t *st = reinterpret_cast<uint32_t *>(a.out) + p;
-                    *st = mck_seed32(reinterpret_cast<const crc32_shift_pack_t *>(a.shift), x, *st, init, n);
+                    if constexpr (SEAL) {
+                        // (the hash slot's neighbours in its 16-byte granule are
+                        // other messages' payload and header bytes: byte stores
+                        // here, and whole-piece stores only inside a payload)
+                        if (!misfit) store_be32(dst + a.hash_off, x ^ xorout);
+                        if (a.status) a.status[p] = misfit ? 1 : 0;
+                    } else {
+                        // (the bytes are stored as received: the value is known only after the copy)
+                        const bool bad = misfit || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
+                        if (a.status) a.status[p] = bad ? 1 : 0;
+                        nbad += bad;
+                    }
                 }
-            } else if constexpr (SEAL) {
-                // In place.  The hash slot shares a 16-byte granule with the
-                // payload's first bytes (slot at 16..19, payload from 20), may
-                // share one with the previous message's tail, and lies in the
-                // pad bytes the previous message's last step reads: payload
-                // loads of this or another wave see its old or its new bytes.
-                // Those bytes are outside every payload, so mck_mask32 clears
-                // them before the fold and no value depends on which.
-                if (gl == 0) {
-                    if (!short_msg) store_be32(reinterpret_cast<uint8_t *>(a.out) + m0 + a.hash_off, x ^ xorout);
-                    if (a.status) a.status[p] = short_msg ? 1 : 0;
-                }
-            } else if (gl == 0) {
-                if (VERIFY && a.msg) {
-                    const bool bad = short_msg || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
-                    if (a.status) a.status[p] = bad ? 1 : 0;
-                    nbad += bad;
-                } else {
-                    emit<uint32_t, VERIFY>(a, p, x ^ xorout, nbad);
+            } else {
+                // bare payloads, or in place (a.msg): a message shorter than its headers fails verification
+                const bool short_msg = a.msg && m1 - m0 < a.pay_off;
+                const uint64_t o = a.msg ? (short_msg ? m1 : m0 + a.pay_off) : m0;
+                const uint64_t n = m1 - o;
+                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
+                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
+                if constexpr (SEED) {
+                    if (gl == 0) {
+                        uint32_t *st = reinterpret_cast<uint32_t *>(a.out) + p;
+                        *st = mck_seed32(reinterpret_cast<const crc32_shift_pack_t *>(a.shift), x, *st, init, n);
+                    }
+                } else if constexpr (SEAL) {
+                    // The hash slot shares a 16-byte granule with the payload's
+                    // first bytes (slot at 16..19, payload from 20), may share one
+                    // with the previous message's tail, and lies in the pad bytes
+                    // the previous message's last step reads: payload loads of this
+                    // or another wave see its old or its new bytes.  Those bytes
+                    // are outside every payload, so mck_mask32 clears them before
+                    // the fold and no value depends on which.
+                    if (gl == 0) {
+                        if (!short_msg) store_be32(a.msgs + m0 + a.hash_off, x ^ xorout);
+                        if (a.status) a.status[p] = short_msg ? 1 : 0;
+                    }
+                } else if (gl == 0) {
+                    if (VERIFY && a.msg) {
+                        const bool bad = short_msg || load_be32(a.base + m0 + a.hash_off) != (x ^ xorout);
+                        if (a.status) a.status[p] = bad ? 1 : 0;
+                        nbad += bad;
+                    } else {
+                        emit<uint32_t, VERIFY>(a, p, x ^ xorout, nbad);
+                    }
                 }
             }
         };

@@ -93,20 +93,36 @@ constexpr int kWpe64 = Shape<64, KEY / 16, false, KEY % 16>::blocks_per_cu * Sha
 
 enum Mode : int { kFixedAligned = 0, kFixedGeneric = 1, kOffsets = 2 };
 
+// The kernels' argument.  One layout for every batch call: a field that a kind
+// of call has no use for carries what that kind needs instead, as a named
+// member of an anonymous union at the same offset -- host and kernels use the
+// name that says what they mean (the host side: offsets_call.h, batch_args_of).
 struct BatchArgs {
     const uint8_t *base;
     const uint64_t *offsets;
-    uint64_t stride, len, count;
-    void *out;
+    uint64_t stride;
+    uint64_t len;  // fixed batches: bytes per payload
+    // whole RPC messages (kFrameRpc): payload_offset in 64 bits, in `len`'s place.  (An accessor, not a member of a
+    // union as below: a union here moved an instruction in every fixed generic CRC-32C kernel.)
+    MCK_HOST_DEVICE uint64_t rpc_pay_off() const { return len; }
+    MCK_HOST_DEVICE void set_rpc_pay_off(uint64_t v) { len = v; }
+    uint64_t count;
+    union {
+        void *out;          // the CRCs; update: the running registers, one per payload, advanced in place
+        uint8_t *msgs;      // the messages, writable: `base` again (a seal in place, of RPC messages), the eager
+                            // messages of the detached calls (a verify only reads them), an RPC pack's (= copy_dst)
+        uint8_t *copy_dst;  // pack and unpack: where the payloads go, by the table dst_offsets
+    };
     union {
         const void *expected;         // verify_offsets: the expected CRCs
-        const uint64_t *dst_offsets;  // pack and unpack: the table of the destination `out`
+        const uint64_t *dst_offsets;  // the table of the other buffer: copy_dst's, the detached calls' msgs'
+        const void *rpc_hdr_pack;     // RPC verify and seal: the header model's pack (launch_plan.h, RpcHdrPack)
     };
     uint8_t *status;
     uint32_t *mismatches;
     const void *pack;
-    // message mode (verify_messages): payload i = [offsets[i] + pay_off,
-    // offsets[i+1]), expected CRC = big-endian u32 at offsets[i] + hash_off
+    // message mode (kFrameInPlace): payload i = [offsets[i] + pay_off,
+    // offsets[i+1]), its CRC the big-endian u32 at offsets[i] + hash_off
     uint32_t msg, pay_off, hash_off;
     // work-queue slot (WgQueue, crc_gpu_queue.h), exclusive to this launch's stream;
     // nullptr = static assignment
@@ -114,12 +130,12 @@ struct BatchArgs {
     // optional caller word (mchecksum_gpu_set_error_word): +1 when this launch
     // could not hash every payload (fail-closed report for checksum modes)
     uint32_t *err_word;
-    // split CRC-64 pieces (crc64_batch_kernel<..., SPLIT>): each payload is
-    // 2^split_log2 pieces of kSplitBytes, recombined with the Z^n shift pack.
-    // Seeded offsets kernels (kOpUpdate, mchecksum_gpu_update_offsets): the
-    // same pack advances the running registers, which `out` then points to
-    // (read and written in place, one element per payload)
-    const void *shift;
+    union {
+        // the Z^n shift pack: recombines the 2^split_log2 pieces of kSplitBytes of a split CRC-64 payload
+        // (crc64_batch_kernel<..., SPLIT>), advances the running registers of an update (kOpUpdate)
+        const void *shift;
+        const void *rpc_copy_hdr_pack;  // RPC pack and unpack: the header pack (their dst_offsets is in use)
+    };
     uint32_t split_log2;
     // MSB-first model on a verify call: the kernel's value is the CRC
     // byte-swapped (crc_gpu_layout.h), so swap before comparing
@@ -128,6 +144,33 @@ struct BatchArgs {
     // so the pieces combine in the workgroup's LDS and out[] needs no zeroing
     uint32_t split_lds;
 };
+// The layout is the kernels' kernarg: pinned here, not by prose.
+#define MCK_AT(S, m, o) static_assert(__builtin_offsetof(S, m) == o, #S "::" #m " moved")
+MCK_AT(BatchArgs, base, 0);
+MCK_AT(BatchArgs, offsets, 8);
+MCK_AT(BatchArgs, stride, 16);
+MCK_AT(BatchArgs, len, 24);
+MCK_AT(BatchArgs, count, 32);
+MCK_AT(BatchArgs, out, 40);
+MCK_AT(BatchArgs, msgs, 40);
+MCK_AT(BatchArgs, copy_dst, 40);
+MCK_AT(BatchArgs, expected, 48);
+MCK_AT(BatchArgs, dst_offsets, 48);
+MCK_AT(BatchArgs, rpc_hdr_pack, 48);
+MCK_AT(BatchArgs, status, 56);
+MCK_AT(BatchArgs, mismatches, 64);
+MCK_AT(BatchArgs, pack, 72);
+MCK_AT(BatchArgs, msg, 80);
+MCK_AT(BatchArgs, pay_off, 84);
+MCK_AT(BatchArgs, hash_off, 88);
+MCK_AT(BatchArgs, queue, 96);
+MCK_AT(BatchArgs, err_word, 104);
+MCK_AT(BatchArgs, shift, 112);
+MCK_AT(BatchArgs, rpc_copy_hdr_pack, 112);
+MCK_AT(BatchArgs, split_log2, 120);
+MCK_AT(BatchArgs, bswap, 124);
+MCK_AT(BatchArgs, split_lds, 128);
+static_assert(sizeof(BatchArgs) == 136 && alignof(BatchArgs) == 8, "BatchArgs changed size");
 // Piece size of a split payload: 256 KiB = 256 steps of the G = 64 loop.
 // (A/B, round 4: 128 KiB pieces +2.9%, 512 KiB +6.8% on C3 time, profiles/r04/ab_split_piece.log)
 constexpr uint64_t kSplitBytes = 256u << 10;

@@ -230,8 +230,8 @@ enum BatchOp : int {
     kOpChecksum,
     // Compares instead of storing: status[p], and the launch's count in
     // *mismatches.  verify_offsets compares with expected[p]; verify_messages
-    // (BatchArgs::msg, a run-time field: the same kernels) with the big-endian
-    // hash in the message's header, and a message shorter than its headers fails.
+    // (kFrameInPlace) with the big-endian hash in the message's header, and a
+    // message shorter than its headers fails.
     kOpVerify,
     // Offsets batches, mchecksum_gpu_update_offsets: instead of storing
     // x ^ xorout, the lane that owns payload p advances the running register
@@ -241,34 +241,45 @@ enum BatchOp : int {
     kOpUpdate,
     // Message mode, mchecksum_gpu_seal_messages: the mirror of the message
     // verify -- the owning lane stores x ^ xorout big-endian in the message's
-    // hash slot (BatchArgs::out = the writable view of base) instead of
+    // hash slot (BatchArgs::msgs) instead of
     // comparing it, and status[p] = 1 only for a message shorter than its
     // headers, which is not written.
     kOpSeal,
     // Seal and copy, mchecksum_gpu_pack_messages: payload p comes from the
     // source table (base, offsets) and is also stored behind the headers of
-    // message p of the destination (out, with its message table in
+    // message p of the destination (copy_dst, with its message table in
     // dst_offsets), by the payload loop itself; a message that does not fit --
     // its size is not pay_off + the payload's -- gets status 1 and no byte
     // written.
     kOpPack,
     // Verify and copy, mchecksum_gpu_unpack_messages: pack's mirror on the
     // receiver -- payload p of the message table (base, offsets) is also stored
-    // at its place in the destination (out, with its table in dst_offsets), and
+    // at its place in the destination (copy_dst, with its table in dst_offsets), and
     // the owning lane's epilogue is the message verify's; a message whose size
     // is not pay_off + its destination's gets status 1, one mismatch and no
     // byte written.
     kOpUnpack,
 };
 
-// Where a verify's or a seal's hash slot is.  In place (false): in the buffer
-// the payloads are in, headers then payload, one table.  Detached (true): an
-// overflow RPC -- the table (base, offsets) addresses the payloads alone, and
-// the slots are in the eager messages, another buffer (BatchArgs::out) with a
-// table of its own (dst_offsets): mchecksum_gpu_verify_detached_messages,
-// mchecksum_gpu_seal_detached_messages.  A key field beside the operation, not
-// an operation: the epilogue is kOpVerify's or kOpSeal's, at another address.
-//
+// What surrounds a payload and where its hash slot is: the one name an entry
+// point gives its call's layout, beside the operation, carried through the host
+// front (offsets_call.h) into the kernels' template arguments.
+enum MsgFrame : int {
+    // bare payloads: checksum_offsets, verify_offsets, update_offsets
+    kFramePayloads,
+    // an HG message, headers then payload in one buffer and one table: verify_messages, seal_messages, and with
+    // the payload moved pack_messages, unpack_messages.  A run-time field of the payloads frame's kernels
+    // (BatchArgs::msg, pay_off, hash_off): kernel_key folds it, and no key says in-place.
+    kFrameInPlace,
+    // an overflow RPC: the table (base, offsets) addresses the payloads alone, and the slots are in the eager
+    // messages, another buffer (BatchArgs::msgs) with a table of its own (dst_offsets): verify_detached_messages,
+    // seal_detached_messages.  The epilogue is kOpVerify's or kOpSeal's, at another address.
+    kFrameDetached,
+    // a whole RPC message -- core header, flags, HG header, payload -- in one pass (the rules below):
+    // verify_rpc_messages, seal_rpc_messages, and with the payload moved unpack_rpc_messages, pack_rpc_messages
+    kFrameRpc,
+};
+
 // The slot rule of the detached calls (and of state_verify_messages and
 // state_seal_messages, which end a streamed pull with the same epilogue):
 // message [m0, m1) carries its slot iff it holds hash_off + 4 bytes -- a table
@@ -290,7 +301,7 @@ constexpr uint64_t kMaxHashOff = 1ull << 30;
 // The core header's CRC-16 runs over the host-order field image, 12 bytes of a
 // request and 4 of a response; bit 0 of its flags byte is HG_CORE_MORE_DATA
 // (src/mercury_core.h:75): the payload is then elsewhere, and neither hashed
-// nor compared here.  The rules below are the kernels' (crc_gpu_crc32.h, RPC)
+// nor compared here.  The rules below are the kernels' (crc_gpu_crc32.h, kFrameRpc)
 // and the CPU's (tests/native/rpc_msg.cpp): the same code.
 constexpr uint64_t kRpcHdrBytes = 16;
 // (MCHECKSUM_GPU_CORE_HEADER_REQUEST / _RESPONSE and MCHECKSUM_GPU_RPC_*; mchecksum_gpu.hip asserts they agree)
@@ -390,7 +401,7 @@ MCK_HOST_DEVICE_INLINE uint32_t rpc_seal_class(uint64_t L, bool more, uint64_t p
     return L < pay_off ? kRpcShort : kRpcOk;
 }
 
-// The copying twins (kOpUnpack, kOpPack with KernelKey::rpc).  R is the length
+// The copying twins (kOpUnpack, kOpPack in kFrameRpc).  R is the length
 // of the other range -- the destination's of an unpack, the source's of a pack
 // (rpc_len of its table entries: backwards is empty).  Whether the payload is
 // copied and hashed: the whole wave's test ahead of its first payload load or
@@ -424,15 +435,11 @@ MCK_HOST_DEVICE_INLINE uint32_t rpc_pack_class(uint64_t L, bool more, uint64_t p
 struct KernelKey {
     int width, lg, mode, op;
     bool nt, light, split;
-    bool detached = false;
-    bool rpc = false;  // whole RPC messages: core header, flags and payload in one pass (the rules above)
-    // ... with the payload moved in the same pass (kOpUnpack, kOpPack): a field of its own, never set with
-    // `rpc`, so the keys `rpc` names stay the six verify and seal twins.  Both are the kernels' RPC argument.
-    bool rpc_copy = false;
+    MsgFrame frame = kFramePayloads;
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split && a.detached == b.detached && a.rpc == b.rpc && a.rpc_copy == b.rpc_copy;
+           a.split == b.split && a.frame == b.frame;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -440,13 +447,18 @@ constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
 constexpr bool kernel_key_valid(const KernelKey &k) {
     if ((k.width != 32 && k.width != 64) || k.lg < 0 || k.lg > CRC_GPU_MAX_LOG2G) return false;
     if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
-    // detached: the message verify and seal of the CRC-32C offsets kernels (light, full, non-temporal)
-    if (k.detached && (k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
-    // rpc: the same six kernels' twins, in place -- never detached
-    if (k.rpc && (k.detached || k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpVerify && k.op != kOpSeal))) return false;
-    // rpc_copy: the twins of the six copying kernels (pack and unpack: light, full, non-temporal)
-    if (k.rpc_copy && (k.rpc || k.detached || k.width != 32 || k.mode != kOffsets || k.split || (k.op != kOpPack && k.op != kOpUnpack)))
-        return false;
+    const bool checks = k.op == kOpVerify || k.op == kOpSeal, copies = k.op == kOpPack || k.op == kOpUnpack;
+    switch (k.frame) {
+        case kFramePayloads: break;
+        // twins of the CRC-32C offsets kernels (light, full, non-temporal), never split: a detached verify or
+        // seal; an RPC verify, seal, pack or unpack
+        case kFrameDetached:
+        case kFrameRpc:
+            if (k.width != 32 || k.mode != kOffsets || k.split) return false;
+            if (!checks && !(k.frame == kFrameRpc && copies)) return false;
+            break;
+        default: return false;  // in place is the payloads frame's kernels (kernel_key)
+    }
     if (k.split)  // pieces of aligned CRC-64 payloads, 64 lanes each: checksums only
         return k.width == 64 && k.mode == kFixedAligned && k.lg == CRC_GPU_MAX_LOG2G && k.op == kOpChecksum;
     switch (k.mode) {
@@ -469,16 +481,9 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
-// The key of a kernel's template arguments.  rpc (the kernels' RPC argument):
-// whole RPC messages -- KernelKey::rpc, or ::rpc_copy for an op that copies.
-constexpr KernelKey kernel_key_of(int width, int lg, int mode, int op, bool nt, bool light, bool split, bool detached, bool rpc) {
-    const bool copy = rpc && (op == kOpPack || op == kOpUnpack);
-    return KernelKey{width, lg, mode, op, nt, light, split, detached, rpc && !copy, copy};
-}
-
-inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, bool detached = false, bool rpc = false) {
-    KernelKey k = kernel_key_of(p.width, p.lg, p.mode, op, p.nt, p.light, p.split, detached, rpc);
-    if (p.split) k = kernel_key_of(64, CRC_GPU_MAX_LOG2G, kFixedAligned, op, p.nt, false, true, detached, rpc);
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, MsgFrame frame = kFramePayloads) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, frame == kFrameInPlace ? kFramePayloads : frame};
+    if (p.split) k.width = 64, k.lg = CRC_GPU_MAX_LOG2G, k.mode = kFixedAligned, k.light = false;
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;
     if (k.light || k.mode == kFixedGeneric) k.nt = false;

@@ -57,6 +57,7 @@
 #include "launch_plan.h"
 #include "mchecksum_gpu.h"
 #include "mchecksum_models.h"
+#include "offsets_call.h"
 #include "seg_plan.h"
 
 namespace mck {
@@ -340,11 +341,11 @@ struct KLaunch {
 };
 
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
-template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, bool DETACHED, bool RPC>
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, MsgFrame FRAME>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(kernel_key_of(W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, DETACHED, RPC))) {
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, FRAME})) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
-        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, DETACHED, RPC>, S::block, S::blocks_per_cu};
+        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, FRAME>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
     return {};
@@ -359,8 +360,7 @@ KLaunch lift(int x, const F &f) {
 
 // The kernel of a key (launch_plan.h: kernel_key): each field becomes a
 // template argument in turn.  A key with no kernel gives a null KLaunch, which
-// the callers report as an error and never launch.  The kernels' RPC argument
-// is the key's rpc or rpc_copy (kernel_key_of: the operation says which).
+// the callers report as an error and never launch.
 KLaunch kernel_for(const KernelKey &k) {
     if (!kernel_key_valid(k)) return {};
     return lift<2>(k.width == 32 ? 0 : k.width == 64 ? 1 : -1, [&](auto w64) {
@@ -370,11 +370,9 @@ KLaunch kernel_for(const KernelKey &k) {
                     return lift<2>(k.nt, [&](auto nt) {
                         return lift<2>(k.light, [&](auto light) {
                             return lift<2>(k.split, [&](auto split) {
-                                return lift<2>(k.detached, [&](auto det) {
-                                    return lift<2>(k.rpc || k.rpc_copy, [&](auto rpc) {
-                                        return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
-                                                          split() != 0, det() != 0, rpc() != 0>();
-                                    });
+                                return lift<kFrameRpc + 1>(k.frame, [&](auto frame) {
+                                    return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
+                                                      split() != 0, (MsgFrame)frame()>();
                                 });
                             });
                         });
@@ -384,37 +382,6 @@ KLaunch kernel_for(const KernelKey &k) {
         });
     });
 }
-
-// One offsets-shaped call, as its entry point names it.  The payloads (or,
-// with msg, the messages that hold them) lie at src by the table src_off.
-struct OffsetsCall {
-    BatchOp op;
-    const char *method;
-    const void *src;
-    const uint64_t *src_off;
-    size_t count;
-    void *out = nullptr;                 // checksum: the CRCs; update: the running registers; seal: src, writable
-    void *dst = nullptr;                 // pack, unpack: where the payloads are copied to, by the table dst_off
-    const uint64_t *dst_off = nullptr;
-    const void *expected = nullptr;      // verify_offsets
-    uint8_t *status = nullptr;
-    uint32_t *mismatches = nullptr;
-    bool msg = false;                    // message mode: payload_offset, hash_offset
-    size_t pay_off = 0, hash_off = 0;
-    void *stream = nullptr;
-    // detached verify and seal (launch_plan.h, KernelKey::detached): src holds the payloads alone, and the
-    // hash slots lie hash_off bytes into the eager messages hdr[hdr_off[i], hdr_off[i + 1])
-    bool detached = false;
-    void *hdr = nullptr;
-    const uint64_t *hdr_off = nullptr;
-    // whole RPC messages (launch_plan.h, KernelKey::rpc): src holds the messages, `out` the same bytes writable
-    // for a seal; the core header's kind and its 16-bit method; pay_off, hash_off; mismatches = the six class counts.
-    // With kOpUnpack / kOpPack (the copying twins) the two buffers and tables are pack's and unpack's -- an unpack's
-    // messages at src, a pack's at dst --, `msg` stays clear, and mismatches = the seven class counts of an unpack
-    bool rpc = false;
-    int kind = 0;
-    const char *hdr_method = nullptr;
-};
 
 // The header pack of a 16-bit model and kind on the device (launch_plan.h,
 // RpcHdrPack), built and uploaded once (under g_mu), then read without a lock.
@@ -452,38 +419,35 @@ static_assert(kRpcRequest == MCHECKSUM_GPU_CORE_HEADER_REQUEST && kRpcResponse =
                   kRpcCopyClasses == MCHECKSUM_GPU_COPY_RPC_CLASSES,
               "launch_plan.h and mchecksum_gpu.h name the kinds and classes alike");
 
-// The front of every offsets-shaped entry point: argument checks, model,
-// device context, plan, table pack, BatchArgs, slot and launch.  The calls on
-// HG messages (seal, pack, unpack) check the method ahead of the device, as an
-// argument (as verify_core_headers does); the others the device first.
+// The front of every offsets-shaped entry point (offsets_call.h: the call, what
+// it must supply, its BatchArgs): argument checks, model, device context, plan,
+// table packs, slot and launch.  The calls on HG and RPC messages but
+// verify_messages check the method ahead of the device, as an argument (as
+// verify_core_headers does); the others the device first.
 int offsets_call(const OffsetsCall &c) {
-    const bool copies = c.op == kOpPack || c.op == kOpUnpack, hg = copies || c.op == kOpSeal || c.detached || c.rpc;
-    const bool stores = c.op == kOpChecksum || c.op == kOpUpdate || (c.op == kOpSeal && !c.detached);
-    // an empty batch needs no buffers (not even the one-entry offsets table)
-    if (c.count && (!c.src || !c.src_off || (stores && !c.out) || (copies && (!c.dst || !c.dst_off)) ||
-                    (c.detached && (!c.hdr || !c.hdr_off)) ||
-                    (c.op == kOpVerify && !c.msg && !c.detached && !c.rpc && !c.expected)))
-        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
-    if (c.rpc && c.kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && c.kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
+    const bool method_first = offsets_needs(c.op, c.frame).method_first;
+    const bool rpc = c.frame == kFrameRpc, detached = c.frame == kFrameDetached, in_place = c.frame == kFrameInPlace;
+    if (offsets_lacks_pointer(c)) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (rpc && c.kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && c.kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
         return set_err(MCHECKSUM_GPU_EINVAL, "unknown core header kind %d", c.kind);
-    if (c.rpc && (c.hash_off < kRpcHdrBytes || c.hash_off > kMaxHashOff || c.hash_off + 4 > c.pay_off))
+    if (rpc && (c.hash_off < kRpcHdrBytes || c.hash_off > kMaxHashOff || c.hash_off + 4 > c.pay_off))
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must lie behind the core header, at most 2^30, and hash_offset + 4 "
                                              "must not exceed payload_offset");
-    if (c.msg && (c.hash_off + 4 > c.pay_off || c.pay_off > (1u << 30)))
+    if (in_place && (c.hash_off + 4 > c.pay_off || c.pay_off > (1u << 30)))
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
-    if (c.detached && c.hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
+    if (detached && c.hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
     if ((uint64_t)c.count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
     Model m;
     int rc;
-    if (hg) {
+    if (method_first) {
         if ((rc = resolve_model(c.method, &m))) return rc;
         if (m.width != 32) return set_err(MCHECKSUM_GPU_EMETHOD, "the HG header carries a 32-bit payload hash: crc32c only");
         // the detached epilogue stores and compares x ^ xorout unswapped: reflected models (both 32-bit ones are)
-        if (c.detached && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no detached message kernel");
-        if (c.rpc && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no RPC message kernel");
+        if (detached && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no detached message kernel");
+        if (rpc && m.msb) return set_err(MCHECKSUM_GPU_EMETHOD, "MSB-first methods have no RPC message kernel");
     }
     int hdr_idx = -1;
-    if (c.rpc) {
+    if (rpc) {
         hdr_idx = mck_model_index(c.hdr_method);
         if (hdr_idx < 0)
             return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", c.hdr_method ? c.hdr_method : "(null)");
@@ -491,42 +455,21 @@ int offsets_call(const OffsetsCall &c) {
             return set_err(MCHECKSUM_GPU_EMETHOD, "core headers carry a 16-bit hash: \"%s\" is not a crc16 model", c.hdr_method);
     }
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
-    if (!hg && (rc = resolve_model(c.method, &m))) return rc;
+    if (!method_first && (rc = resolve_model(c.method, &m))) return rc;
     DevCtx *dc = nullptr;
-    const void *pack = nullptr, *shift = nullptr;
+    const void *pack = nullptr, *shift = nullptr, *hdr_pack = nullptr;
     if ((rc = device_ctx(&dc))) return rc;
     const LaunchPlan p = plan_offsets(*mck_settings(), dc->cus, m.width, c.count);
     // (an empty batch too resolves its method and builds its tables)
     if ((rc = get_pack(dc, m.idx, p.lg, &pack))) return rc;
     if (c.op == kOpUpdate && (rc = get_ext(dc, m.idx, &shift))) return rc;
-    const void *hdr_pack = nullptr;
-    if (c.rpc && (rc = get_rpc_pack(dc, hdr_idx, c.kind, &hdr_pack))) return rc;
+    if (rpc && (rc = get_rpc_pack(dc, hdr_idx, c.kind, &hdr_pack))) return rc;
     if (c.count == 0) return MCHECKSUM_GPU_OK;
-    if (c.msg && m.width != 32)
+    if (in_place && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const KLaunch k = kernel_for(kernel_key(p, c.op, c.detached, c.rpc));
+    const KLaunch k = kernel_for(kernel_key(p, c.op, c.frame));
     if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
-    BatchArgs a{};
-    a.base = (const uint8_t *)c.src;
-    a.offsets = c.src_off;
-    a.count = c.count;
-    // (a detached verify or seal stores no values and copies nothing: `out` and the union are free for the messages)
-    a.out = copies ? c.dst : c.detached ? c.hdr : c.out;
-    if (copies) a.dst_offsets = c.dst_off;
-    else if (c.detached) a.dst_offsets = c.hdr_off;
-    else if (c.rpc) a.expected = hdr_pack;  // (compares by header, stores no values: the pointer is free for the 16-bit model)
-    else a.expected = c.expected;
-    if (c.rpc) a.len = c.pay_off;  // in 64 bits: a fixed batch's field, free in an offsets batch
-    a.status = c.status;
-    a.mismatches = c.mismatches;
-    a.pack = pack;
-    a.msg = c.msg ? 1u : 0u;
-    a.pay_off = (uint32_t)c.pay_off;
-    a.hash_off = (uint32_t)c.hash_off;
-    a.err_word = error_word();
-    a.bswap = c.op == kOpVerify && m.msb ? 1u : 0u;  // checksum calls swap after the launch
-    a.shift = shift;
-    if (c.rpc && copies) a.shift = hdr_pack;  // (`expected` is the destination's table here; no update, no split: free)
+    BatchArgs a = batch_args_of(c, pack, shift, hdr_pack, m.msb, error_word());
     SlotRef sr;
     if (p.dyn) sr = queue_slot(dc, c.stream);
     a.queue = sr.q;
@@ -1040,7 +983,7 @@ int mchecksum_gpu_verify_messages(const char *hash_method, const void *dev_buf, 
                                   size_t count, size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
                                   uint32_t *dev_mismatches, void *stream) {
     OffsetsCall c{kOpVerify, hash_method, dev_buf, dev_msg_offsets, count};
-    c.msg = true;
+    c.frame = kFrameInPlace;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;
@@ -1053,7 +996,7 @@ int mchecksum_gpu_seal_messages(const char *hash_method, void *dev_buf, const ui
                                 size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
     OffsetsCall c{kOpSeal, hash_method, dev_buf, dev_msg_offsets, count};  // in place: the payloads are dev_buf's own
     c.out = dev_buf;
-    c.msg = true;
+    c.frame = kFrameInPlace;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;
@@ -1068,7 +1011,7 @@ int mchecksum_gpu_pack_messages(const char *hash_method, const void *dev_src, co
     OffsetsCall c{kOpPack, hash_method, dev_src, dev_src_offsets, count};
     c.dst = dev_buf;
     c.dst_off = dev_msg_offsets;
-    c.msg = true;
+    c.frame = kFrameInPlace;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;
@@ -1084,7 +1027,7 @@ int mchecksum_gpu_unpack_messages(const char *hash_method, const void *dev_buf, 
     OffsetsCall c{kOpUnpack, hash_method, dev_buf, dev_msg_offsets, count};
     c.dst = dev_dst;
     c.dst_off = dev_dst_offsets;
-    c.msg = true;
+    c.frame = kFrameInPlace;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;
@@ -1099,7 +1042,7 @@ int mchecksum_gpu_verify_detached_messages(const char *hash_method, const void *
                                            uint32_t *dev_mismatches, void *stream) {
     // an overflow RPC: the payloads are the batch, the eager messages only carry the hashes (and are only read)
     OffsetsCall c{kOpVerify, hash_method, dev_payloads, dev_payload_offsets, count};
-    c.detached = true;
+    c.frame = kFrameDetached;
     c.hdr = const_cast<void *>(dev_msgs);
     c.hdr_off = dev_msg_offsets;
     c.hash_off = hash_offset;
@@ -1114,7 +1057,7 @@ int mchecksum_gpu_seal_detached_messages(const char *hash_method, void *dev_msgs
                                          const uint64_t *dev_payload_offsets, size_t count, uint8_t *dev_status,
                                          void *stream) {
     OffsetsCall c{kOpSeal, hash_method, dev_payloads, dev_payload_offsets, count};
-    c.detached = true;
+    c.frame = kFrameDetached;
     c.hdr = dev_msgs;
     c.hdr_off = dev_msg_offsets;
     c.hash_off = hash_offset;
@@ -1127,7 +1070,7 @@ int mchecksum_gpu_verify_rpc_messages(const char *header_method, const char *pay
                                       const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                       size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
     OffsetsCall c{kOpVerify, payload_method, dev_buf, dev_msg_offsets, count};
-    c.rpc = true;
+    c.frame = kFrameRpc;
     c.kind = kind;
     c.hdr_method = header_method;
     c.pay_off = payload_offset;
@@ -1142,7 +1085,7 @@ int mchecksum_gpu_seal_rpc_messages(const char *header_method, const char *paylo
                                     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                     size_t hash_offset, uint8_t *dev_status, void *stream) {
     OffsetsCall c{kOpSeal, payload_method, dev_buf, dev_msg_offsets, count};
-    c.rpc = true;
+    c.frame = kFrameRpc;
     c.kind = kind;
     c.hdr_method = header_method;
     c.out = dev_buf;
@@ -1159,7 +1102,7 @@ int mchecksum_gpu_unpack_rpc_messages(const char *header_method, const char *pay
                                       uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
     // unpack_messages' buffers under verify_rpc_messages' rules: the messages are the source
     OffsetsCall c{kOpUnpack, payload_method, dev_buf, dev_msg_offsets, count};
-    c.rpc = true;
+    c.frame = kFrameRpc;
     c.kind = kind;
     c.hdr_method = header_method;
     c.dst = dev_dst;
@@ -1178,7 +1121,7 @@ int mchecksum_gpu_pack_rpc_messages(const char *header_method, const char *paylo
                                     void *stream) {
     // pack_messages' buffers under seal_rpc_messages' rules: the headers (and their flags) are read from dev_buf
     OffsetsCall c{kOpPack, payload_method, dev_src, dev_src_offsets, count};
-    c.rpc = true;
+    c.frame = kFrameRpc;
     c.kind = kind;
     c.hdr_method = header_method;
     c.dst = dev_buf;

@@ -239,6 +239,13 @@ static const struct {
     {"no such lane count", {32, 7, kFixedAligned, kOpChecksum, 0, 0, 0}},
     {"no such mode", {32, 6, 3, kOpChecksum, 0, 0, 0}},
     {"no such operation", {32, 6, kOffsets, kOpUnpack + 1, 0, 0, 0}},
+    {"in place is no key's frame (kernel_key folds it)", {32, 6, kOffsets, kOpVerify, 0, 0, 0, kFrameInPlace}},
+    {"no such frame", {32, 6, kOffsets, kOpVerify, 0, 0, 0, (MsgFrame)(kFrameRpc + 1)}},
+    {"detached pack", {32, 6, kOffsets, kOpPack, 0, 0, 0, kFrameDetached}},
+    {"detached checksum", {32, 6, kOffsets, kOpChecksum, 0, 0, 0, kFrameDetached}},
+    {"RPC update", {32, 6, kOffsets, kOpUpdate, 0, 0, 0, kFrameRpc}},
+    {"crc64 RPC verify", {64, 6, kOffsets, kOpVerify, 0, 0, 0, kFrameRpc}},
+    {"RPC verify of a fixed batch", {32, 6, kFixedAligned, kOpVerify, 0, 0, 0, kFrameRpc}},
 };
 
 // choose_log2g(width, len) with nothing forced
@@ -377,6 +384,17 @@ int main() {
                         }
         CHECK(n[0] == 35 && n[1] == 21 && n[2] == 2 && n[3] == 15 && n[4] == 9, "valid keys: %d %d %d %d %d", n[0], n[1], n[2],
               n[3], n[4]);
+        // ... and in the other frames (MsgFrame): 6 detached, 12 RPC, none in place or past the last
+        int nf[kFrameRpc + 2] = {};
+        for (int frame = kFrameInPlace; frame <= kFrameRpc + 1; frame++)
+            for (int width : {16, 32, 64})
+                for (int lg = -1; lg <= CRC_GPU_MAX_LOG2G + 1; lg++)
+                    for (int mode = -1; mode <= kOffsets + 1; mode++)
+                        for (int op = -1; op <= kOpUnpack + 1; op++)
+                            for (int f = 0; f < 8; f++)
+                                nf[frame] += kernel_key_valid(KernelKey{width, lg, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (MsgFrame)frame});
+        CHECK(nf[kFrameInPlace] == 0 && nf[kFrameDetached] == 6 && nf[kFrameRpc] == 12 && nf[kFrameRpc + 1] == 0,
+              "valid keys by frame: %d %d %d %d", nf[kFrameInPlace], nf[kFrameDetached], nf[kFrameRpc], nf[kFrameRpc + 1]);
     }
     const mck_settings_t d = D.snapshot();
     for (const auto &r : kLanes) CHECK(choose_log2g(d, r.len, r.width) == r.lg, "choose_log2g(%zu, %d) = %d", r.len, r.width, choose_log2g(d, r.len, r.width));

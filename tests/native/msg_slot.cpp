@@ -88,16 +88,27 @@ int main() {
         for (int width : {32, 64})
             for (int mode = 0; mode <= kOffsets; mode++)
                 for (int f = 0; f < 8; f++) {
-                    const mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, true};
+                    const mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, mck::kFrameDetached};
                     if (!mck::kernel_key_valid(k)) continue;
                     n++;
                     CHECK(width == 32 && mode == kOffsets && !k.split && !(k.nt && k.light));
                     CHECK(op == mck::kOpVerify || op == mck::kOpSeal);
+                    // its sibling in place: the payloads frame's kernel (kernel_key folds kFrameInPlace into it)
                     mck::KernelKey in_place = k;
-                    in_place.detached = false;
+                    in_place.frame = mck::kFramePayloads;
                     CHECK(mck::kernel_key_valid(in_place) && !(in_place == k));
                 }
     CHECK(n == 6);
+    {
+        // kernel_key(plan, op, frame) yields them, and kernel_key(plan, op) does not
+        mck::LaunchPlan p;
+        p.width = 32, p.lg = CRC_GPU_MAX_LOG2G, p.mode = kOffsets;
+        for (mck::BatchOp op : {mck::kOpVerify, mck::kOpSeal}) {
+            const mck::KernelKey k = mck::kernel_key(p, op, mck::kFrameDetached);
+            CHECK(mck::kernel_key_valid(k) && k.frame == mck::kFrameDetached && k.op == op);
+            CHECK(mck::kernel_key(p, op).frame == mck::kFramePayloads);
+        }
+    }
     std::printf("%llu messages: %llu with a slot, %llu without\n", msgs, with_slot, without);
     if (g_fail) {
         std::printf("%d checks failed\n", g_fail);

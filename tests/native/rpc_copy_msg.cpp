@@ -308,31 +308,39 @@ int main() {
         CHECK(mck::rpc_pack_class(16, true, 20, R) == mck::kRpcDeferred);
         CHECK(!mck::rpc_copies_payload(16 + R, true, 20, R));
     }
-    // the kernels there are for the copying calls: light, full, non-temporal, pack and unpack -- a key field of
-    // their own, never with `rpc` or `detached`; kernel_key names them from the call's operation
-    int n = 0;
+    // the kernels there are for the copying calls: light, full, non-temporal, pack and unpack -- the RPC frame's
+    // keys with a copying operation (its six others: verify and seal, rpc_msg.cpp); no other frame but the
+    // payloads' has a copying key, and kernel_key names them from the call's operation and frame
+    int n = 0, n_check = 0;
     for (int op = -1; op <= mck::kOpUnpack + 1; op++)
         for (int width : {32, 64})
             for (int mode = 0; mode <= kOffsets; mode++)
-                for (int f = 0; f < 32; f++) {
-                    mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (f & 8) != 0, (f & 16) != 0};
-                    k.rpc_copy = true;
-                    if (!mck::kernel_key_valid(k)) continue;
-                    n++;
-                    CHECK(width == 32 && mode == kOffsets && !k.split && !k.detached && !k.rpc && !(k.nt && k.light));
-                    CHECK(op == mck::kOpPack || op == mck::kOpUnpack);
-                    mck::KernelKey plain = k;
-                    plain.rpc_copy = false;
-                    CHECK(mck::kernel_key_valid(plain) && !(plain == k));
-                }
-    CHECK(n == 6);
+                for (int f = 0; f < 8; f++)
+                    for (int frame = -1; frame <= mck::kFrameRpc + 1; frame++) {
+                        const mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (mck::MsgFrame)frame};
+                        const bool copy = op == mck::kOpPack || op == mck::kOpUnpack;
+                        if (!mck::kernel_key_valid(k) || frame == mck::kFramePayloads) continue;
+                        CHECK(frame == mck::kFrameRpc || (frame == mck::kFrameDetached && !copy));
+                        if (frame != mck::kFrameRpc) continue;
+                        (copy ? n : n_check)++;
+                        CHECK(width == 32 && mode == kOffsets && !k.split && !(k.nt && k.light));
+                        CHECK(copy || op == mck::kOpVerify || op == mck::kOpSeal);
+                        mck::KernelKey plain = k;
+                        plain.frame = mck::kFramePayloads;
+                        CHECK(mck::kernel_key_valid(plain) && !(plain == k));
+                    }
+    CHECK(n == 6 && n_check == 6);
     mck::LaunchPlan p;
     p.width = 32, p.lg = CRC_GPU_MAX_LOG2G, p.mode = kOffsets;
     for (int op : {mck::kOpVerify, mck::kOpSeal, mck::kOpPack, mck::kOpUnpack}) {
-        const mck::KernelKey k = mck::kernel_key(p, (mck::BatchOp)op, false, true);
-        const bool copy = op == mck::kOpPack || op == mck::kOpUnpack;
-        CHECK(mck::kernel_key_valid(k) && k.rpc == !copy && k.rpc_copy == copy);
-        CHECK(!mck::kernel_key(p, (mck::BatchOp)op).rpc_copy && !mck::kernel_key(p, (mck::BatchOp)op).rpc);
+        const mck::KernelKey k = mck::kernel_key(p, (mck::BatchOp)op, mck::kFrameRpc);
+        CHECK(mck::kernel_key_valid(k) && k.frame == mck::kFrameRpc && k.op == op);
+        CHECK(mck::kernel_key(p, (mck::BatchOp)op).frame == mck::kFramePayloads);
+        // in place is a run-time field of the payloads frame's kernels: folded by kernel_key, and no key says it
+        CHECK(mck::kernel_key(p, (mck::BatchOp)op, mck::kFrameInPlace) == mck::kernel_key(p, (mck::BatchOp)op));
+        mck::KernelKey in_place = k;
+        in_place.frame = mck::kFrameInPlace;
+        CHECK(!mck::kernel_key_valid(in_place));
     }
     std::printf("%llu messages: ok %llu payload %llu header %llu short %llu deferred %llu misfit %llu\n", msgs, seen[OK],
                 seen[PAYLOAD], seen[HEADER], seen[SHORT], seen[DEFERRED], seen[MISFIT]);

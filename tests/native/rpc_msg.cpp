@@ -235,22 +235,43 @@ int main() {
     // a payload_offset past 2^32 is not truncated
     CHECK(mck::rpc_verify_class(1ull << 33, true, false, (1ull << 40), true) == mck::kRpcShort);
     CHECK(mck::rpc_seal_class(1ull << 33, false, (1ull << 40)) == mck::kRpcShort);
-    // the kernels there are for the RPC calls: light, full, non-temporal, verify and seal -- never detached
-    int n = 0;
+    // the kernels there are for the RPC calls: light, full, non-temporal, verify and seal -- six keys of the RPC
+    // frame; its other six are the copying twins' (rpc_copy_msg.cpp), and a key has one frame: never detached
+    int n = 0, n_copy = 0;
     for (int op = -1; op <= mck::kOpUnpack + 1; op++)
         for (int width : {32, 64})
             for (int mode = 0; mode <= kOffsets; mode++)
-                for (int f = 0; f < 16; f++) {
-                    const mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (f & 8) != 0, true};
+                for (int f = 0; f < 8; f++) {
+                    const mck::KernelKey k{width, CRC_GPU_MAX_LOG2G, mode, op, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, mck::kFrameRpc};
                     if (!mck::kernel_key_valid(k)) continue;
-                    n++;
-                    CHECK(width == 32 && mode == kOffsets && !k.split && !k.detached && !(k.nt && k.light));
-                    CHECK(op == mck::kOpVerify || op == mck::kOpSeal);
+                    const bool copy = op == mck::kOpPack || op == mck::kOpUnpack;
+                    (copy ? n_copy : n)++;
+                    CHECK(width == 32 && mode == kOffsets && !k.split && k.frame != mck::kFrameDetached && !(k.nt && k.light));
+                    CHECK(copy || op == mck::kOpVerify || op == mck::kOpSeal);
                     mck::KernelKey plain = k;
-                    plain.rpc = false;
+                    plain.frame = mck::kFramePayloads;
                     CHECK(mck::kernel_key_valid(plain) && !(plain == k));
                 }
-    CHECK(n == 6);
+    CHECK(n == 6 && n_copy == 6);
+    {
+        // kernel_key(plan, op, frame) yields them, and kernel_key(plan, op) does not
+        mck::LaunchPlan p;
+        p.width = 32, p.lg = CRC_GPU_MAX_LOG2G, p.mode = kOffsets;
+        for (mck::BatchOp op : {mck::kOpVerify, mck::kOpSeal}) {
+            const mck::KernelKey k = mck::kernel_key(p, op, mck::kFrameRpc);
+            CHECK(mck::kernel_key_valid(k) && k.frame == mck::kFrameRpc && k.op == op);
+            CHECK(mck::kernel_key(p, op).frame == mck::kFramePayloads);
+        }
+    }
+    {
+        // kernel_key(plan, op, frame) yields them, and kernel_key(plan, op) does not
+        mck::LaunchPlan p;
+        p.width = 32, p.lg = CRC_GPU_MAX_LOG2G, p.mode = kOffsets;
+        for (mck::BatchOp op : {mck::kOpVerify, mck::kOpSeal}) {
+            CHECK(mck::kernel_key_valid(mck::kernel_key(p, op, mck::kFrameRpc)) && mck::kernel_key(p, op, mck::kFrameRpc).frame == mck::kFrameRpc);
+            CHECK(mck::kernel_key(p, op).frame == mck::kFramePayloads);
+        }
+    }
     std::printf("%llu messages: ok %llu payload %llu header %llu short %llu deferred %llu\n", msgs, seen[0], seen[1], seen[2], seen[3],
                 seen[4]);
     if (g_fail) {

@@ -22,10 +22,14 @@ A kernel's key is read from its demangled template arguments, in either
 spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
 and crc64_batch_kernel<LOG2G, MODE, VERIFY, NT, SPLIT, SEED> (bool packs), or
 <LOG2G, MODE, OP, NT, LIGHT> and <LOG2G, MODE, OP, NT, SPLIT> (BatchOp,
-launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED[, RPC]> (KernelKey::detached:
-such a kernel's operation reads "verify_detached" / "seal_detached"; KernelKey::rpc:
-"verify_rpc" / "seal_rpc", and "pack_rpc" / "unpack_rpc" for the copying twins).  Exit status 1 unless the pairing is one to one and every pair
-is equal in everything.
+launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED[, RPC]> (two bools),
+or <LOG2G, MODE, OP, NT, LIGHT, FRAME> (MsgFrame, launch_plan.h: the enum's
+type is part of the demangled name, "(mck::MsgFrame)3", which tells it from the
+bool spelling).  In the last two a detached kernel's operation reads
+"verify_detached" / "seal_detached" and a whole-RPC kernel's "verify_rpc" /
+"seal_rpc" / "pack_rpc" / "unpack_rpc", so both spellings pair by what a kernel
+is.  Exit status 1 unless the pairing is one to one and every pair is equal in
+everything.
 """
 import hashlib
 import os
@@ -33,7 +37,7 @@ import re
 import subprocess
 import sys
 
-from resource_diff import KEYS, parse
+from resource_diff import KEYS, parse, strip_params
 
 OPS = ["checksum", "verify", "update", "seal", "pack", "unpack"]
 MODES = ["aligned", "generic", "offsets"]
@@ -46,15 +50,19 @@ def key_of(name):
     if not m:
         return None
     width = 32 if m.group(1) == "32c" else 64
-    a = [{"true": 1, "false": 0}.get(t.strip(), t.strip()) for t in m.group(2).split(",")]
+    raw = [t.strip() for t in m.group(2).split(",")]
+    a = [{"true": 1, "false": 0}.get(t, t) for t in raw]
     a = [int(re.sub(r"^\(.*\)", "", t)) if isinstance(t, str) else t for t in a]
     lg, mode = a[0], a[1]
-    if len(a) == 5 or (len(a) in (6, 7) and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED[, RPC]]>
+    if len(a) == 5 or (len(a) in (6, 7) and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED[, RPC] or FRAME]>
         op, nt, last = a[2], a[3], a[4]
         light, split = (last, 0) if width == 32 else (0, last)
-        if len(a) >= 6 and a[5]:  # KernelKey::detached: the slot of a verify or a seal in another buffer
+        if len(a) == 6 and "MsgFrame" in raw[5]:  # MsgFrame: payloads (in place is a run-time field), -, detached, RPC
+            frame = ["", None, "_detached", "_rpc"][a[5]]
+            return (width, lg, MODES[mode], OPS[op] + frame, nt, light, split)
+        if len(a) >= 6 and a[5]:  # DETACHED: the slot of a verify or a seal in another buffer
             return (width, lg, MODES[mode], OPS[op] + "_detached", nt, light, split)
-        if len(a) == 7 and a[6]:  # KernelKey::rpc: whole RPC messages, header and flags with the payload
+        if len(a) == 7 and a[6]:  # RPC: whole RPC messages, header and flags with the payload
             return (width, lg, MODES[mode], OPS[op] + "_rpc", nt, light, split)
     else:  # the bool packs
         verify, nt = a[2], a[3]
@@ -108,12 +116,12 @@ def load(d, asm_name=ASM):
         short = re.sub(r"\(anonymous namespace\)::|^void ", "", names[mangled])
         k = key_of(short)
         if k is None:  # the element kernels and the device functions the batch kernels call: by name
-            short = re.sub(r"\(.*\)$", "", short)
+            short = strip_params(short)
             k = (0, 0, "-", short, 0, 0, 0)
         elif not short.startswith("crc"):  # a function one batch kernel did not inline: by that kernel and its own name
             k = k + (short.split("<")[0],)
         else:
-            short = re.sub(r"\(.*\)$", "", short)
+            short = strip_params(short)
         if k in rows:
             sys.exit(f"{d}: two functions with key {k}")
         rows[k] = dict(sha=sha, insts=n, code=size, res=[res.get(short, {}).get(x, "-") for x in KEYS])

@@ -17,6 +17,17 @@ KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [
 SHORT = ["VGPR", "AGPR", "SGPR", "scratch", "occ", "SGPR spill", "VGPR spill", "LDS"]
 
 
+def strip_params(name):
+    """A demangled function name without its trailing parameter list.  (Not by a greedy pattern from the first
+    parenthesis: an enum template argument is spelled with one, "(mck::MsgFrame)3".)"""
+    depth = 0
+    for i in range(len(name) - 1, -1, -1):
+        depth += (name[i] == ")") - (name[i] == "(")
+        if depth == 0:
+            return name[:i] if name.endswith(")") else name
+    return name
+
+
 def parse(path):
     rows, cur = {}, None
     for line in open(path):
@@ -26,7 +37,7 @@ def parse(path):
         txt = m.group(1).strip()
         if txt.startswith("Function Name:"):
             name = subprocess.run(["c++filt", txt.split(":", 1)[1].strip()], capture_output=True, text=True).stdout.strip()
-            name = re.sub(r"\(anonymous namespace\)::|^void |\(.*\)$", "", name)
+            name = strip_params(re.sub(r"\(anonymous namespace\)::|^void ", "", name))
             cur = rows.setdefault(name, {})
         elif cur is not None and ":" in txt:
             k, v = txt.split(":", 1)
