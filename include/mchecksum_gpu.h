@@ -996,6 +996,77 @@ mchecksum_gpu_pack_rpc_messages(const char *header_method,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, uint8_t *dev_status, void *stream);
 
+/* The four calls above with the message side addressed by a LIST: what a
+ * receiver holds after draining several multi-recv buffers (one actual_buf /
+ * actual_buf_size pair per completion, src/na/na_types.h:187), and what a
+ * sender holds with an out_buf per handle.  One table cannot name messages
+ * that lie in several allocations, with gaps, in any order; two arrays can.
+ *
+ * Message side.  Message i is the dev_msg_len[i] bytes at the device address
+ * dev_msg_addr[i]: both arrays are device-resident, `count` entries each (not
+ * count + 1), as dev_seg_addr / dev_seg_len of the segment calls.  L =
+ * dev_msg_len[i]; a message whose end would pass the end of the address space
+ * counts as L = 0, as a table that runs backwards does.  Messages may lie in
+ * any number of allocations, in any order, with any gaps, at any byte
+ * alignment.  Messages that are WRITTEN (seal, pack) must not overlap one
+ * another; an unpack's destination and a pack's source must not overlap the
+ * messages.
+ *
+ * Other side (unpack, pack): the table form as it is -- dev_dst / dev_src with
+ * count + 1 offsets, R and the backwards rule as above.  A list on both sides
+ * is not offered.
+ *
+ * Inherited word for word, not restated: the rule ladders and the statuses of
+ * the table call of the same name, dev_counts (6 words for verify, 7 for
+ * unpack), exactly which bytes are written, "what is written does not wait
+ * for the verdicts", both header bit orders and a reflected 32-bit payload
+ * method, the argument bounds and their order (EINVAL, then both methods
+ * EMETHOD ahead of the device, then ENODEV; dev_msg_addr and dev_msg_len are
+ * required pointers with count > 0; count == 0 needs no buffers but passes the
+ * checks first), the launch rules, and the fail-closed rules.  Capture-safe
+ * after mchecksum_gpu_prepare() of BOTH methods; a replay reads the current
+ * contents of both arrays, so a captured call serves the next drain by
+ * rewriting them in place.  No workspace, one launch: a twin of the kernel
+ * the table call picks for the same count.
+ *
+ * Reads.  Per message, in aligned 16-byte pieces that stay inside the aligned
+ * 128-byte lines holding the first and the last byte the call reads of that
+ * message: any message lying inside a device allocation satisfies this, and
+ * nothing between, before or behind messages is read into a verdict.  A
+ * message with L < 16 is SHORT and its address is never dereferenced (it may
+ * be NULL).  A DEFERRED message is read in its first 16 bytes only, and so is
+ * an eager one shorter than payload_offset or -- unpack, pack -- one that
+ * does not fit.  Nothing outside the messages and the other range is written.
+ * DESIGN.md 4.25 has the design and the measurements against the table calls.
+ * Not yet: the DEFERRED messages of a list cannot go to
+ * mchecksum_gpu_verify_detached_messages as they are (it reads its slots
+ * through a table). */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_rpc_message_list(const char *header_method,
+    const char *payload_method, int kind, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_rpc_message_list(const char *header_method,
+    const char *payload_method, int kind, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_rpc_message_list(const char *header_method,
+    const char *payload_method, int kind, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t count, size_t payload_offset,
+    size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+    uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_rpc_message_list(const char *header_method,
+    const char *payload_method, int kind, const void *dev_src,
+    const uint64_t *dev_src_offsets, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t count, size_t payload_offset,
+    size_t hash_offset, uint8_t *dev_status, void *stream);
+
 /* XDR-mode proc checksum.  In a Mercury built with
  * MERCURY_USE_XDR (HG_HAS_XDR) the serialized buffer holds XDR -- every
  * integer big-endian and rounded up to 4 bytes, byte arrays zero-padded to a

@@ -39,7 +39,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_seal_detached_messages", "mchecksum_gpu_state_verify_messages",
                "mchecksum_gpu_state_seal_messages", "mchecksum_gpu_verify_rpc_messages",
                "mchecksum_gpu_seal_rpc_messages", "mchecksum_gpu_unpack_rpc_messages",
-               "mchecksum_gpu_pack_rpc_messages")
+               "mchecksum_gpu_pack_rpc_messages", "mchecksum_gpu_verify_rpc_message_list",
+               "mchecksum_gpu_seal_rpc_message_list", "mchecksum_gpu_unpack_rpc_message_list",
+               "mchecksum_gpu_pack_rpc_message_list")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -210,6 +212,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_pack_rpc_messages.argtypes = [c_char_p, c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_size_t, c_size_t, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_pack_rpc_messages.restype = c_int
+    # the message side by address list: (msg_addr, msg_len) where the table calls have (buf, msg_offsets)
+    L.mchecksum_gpu_verify_rpc_message_list.argtypes = L.mchecksum_gpu_verify_rpc_messages.argtypes
+    L.mchecksum_gpu_verify_rpc_message_list.restype = c_int
+    L.mchecksum_gpu_seal_rpc_message_list.argtypes = L.mchecksum_gpu_seal_rpc_messages.argtypes
+    L.mchecksum_gpu_seal_rpc_message_list.restype = c_int
+    L.mchecksum_gpu_unpack_rpc_message_list.argtypes = L.mchecksum_gpu_unpack_rpc_messages.argtypes
+    L.mchecksum_gpu_unpack_rpc_message_list.restype = c_int
+    L.mchecksum_gpu_pack_rpc_message_list.argtypes = L.mchecksum_gpu_pack_rpc_messages.argtypes
+    L.mchecksum_gpu_pack_rpc_message_list.restype = c_int
     L.mchecksum_gpu_pack_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                               c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_pack_messages.restype = c_int

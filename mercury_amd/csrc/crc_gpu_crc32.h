@@ -440,16 +440,25 @@ __device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
 // OP the payload is also stored by the payload loop, and the other range's
 // length enters the rules (rpc_copies_payload, rpc_unpack_class,
 // rpc_pack_class).  In place is the payloads frame's kernels (BatchArgs::msg).
-template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, mck::MsgFrame FRAME = mck::kFramePayloads>
+// LIST (launch_plan.h, KernelKey::list; kFrameRpc only): the message side is an
+// address list -- its table entry p is the message's absolute address, used with
+// a null buffer pointer, and its end that address + len[p] from a second array
+// (BatchArgs::rpc_list_len) where the table form reads entry p + 1.  Nothing
+// else differs but what follows from messages that lie anywhere: a message
+// whose payload is not hashed runs the empty payload at address 0 -- no load,
+// where the table form's may read on in the line of the message's end --, and
+// the light layout deals messages by count, there being no table to balance by.
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, mck::MsgFrame FRAME = mck::kFramePayloads, bool LIST = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, FRAME}), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, FRAME, LIST}), "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
         SEED = OP == mck::kOpUpdate,
         SEAL = OP == mck::kOpSeal || OP == mck::kOpPack,
         COPY = OP == mck::kOpPack || OP == mck::kOpUnpack,
-        RPC = FRAME == mck::kFrameRpc
+        RPC = FRAME == mck::kFrameRpc,
+        LIST_BATCH = LIST && !(COPY && SEAL)  // the list is the batch's own side (a pack's is the written side)
     };
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
@@ -509,7 +518,8 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
 
     if (MODE == kOffsets) {
         auto one = [&](uint64_t p) {
-            const uint64_t m0 = a.offsets[p], m1 = a.offsets[p + 1];
+            // (LIST: entry p is an address and the array has no entry `count`; an end that wraps is an empty message)
+            const uint64_t m0 = a.offsets[p], m1 = LIST_BATCH ? m0 + a.rpc_list_len()[p] : a.offsets[p + 1];
             if constexpr (RPC) {
                 // A whole RPC message.  Lanes 0..15 load a header byte each and
                 // look up its term of the CRC-16 (launch_plan.h, RpcHdrPack:
@@ -531,7 +541,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 uint64_t g0 = m0, g1 = m1;
                 const uint8_t *mbuf = a.base;
                 if constexpr (COPY && SEAL) {
-                    g0 = a.dst_offsets[p], g1 = a.dst_offsets[p + 1];
+                    g0 = a.dst_offsets[p], g1 = LIST ? g0 + a.rpc_list_len()[p] : a.dst_offsets[p + 1];
                     mbuf = a.msgs;
                 }
                 const uint64_t L = mck::rpc_len(g0, g1);
@@ -549,13 +559,19 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 uint32_t x;
                 if constexpr (COPY) {
                     // (an unpack reads [m0 + pay, m0 + L), a pack [m0, m0 + R): R bytes either way)
-                    const uint64_t o = SEAL ? m0 : m0 + pay, n = hashed ? R : 0;
+                    // (LIST_BATCH: a message that is not copied may lie anywhere, or nowhere: its empty payload is
+                    // address 0's, a grid window of no step)
+                    uint64_t o = SEAL ? m0 : m0 + pay;
+                    const uint64_t n = hashed ? R : 0;
+                    if constexpr (LIST_BATCH) o = hashed ? o : 0;
                     uint8_t *dst = a.copy_dst + (SEAL ? g0 + pay : a.dst_offsets[p]);
                     x = n < (1ull << 31)
                             ? payload32_g64<NT, Tab32<LIGHT>, false, true>(lds, pk, a.base + o, n, gl, lc0, lc1, 0u, dst)
                             : payload32_generic<LOG2G, NT, Tab32<LIGHT>, true>(lds, pk, a.base + o, n, gl, lc0, lc1, dst);
                 } else {
-                    const uint64_t o = hashed ? m0 + pay : m0 + L, n = m0 + L - o;
+                    uint64_t o = hashed ? m0 + pay : m0 + L;
+                    const uint64_t n = m0 + L - o;
+                    if constexpr (LIST) o = hashed ? o : 0;  // (as above: address 0's empty payload)
                     x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
                                          : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
                 }
@@ -683,7 +699,13 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
             }
         } else {  // static: a byte-balanced contiguous range per wave
             uint64_t first, last;
-            wave_range(a.offsets, a.count, wave, nw, &first, &last);
+            if constexpr (LIST_BATCH) {  // addresses are no table to balance bytes by: a contiguous range by count
+                const uint64_t q = a.count / nw, r = a.count % nw;
+                first = q * wave + (r * wave) / nw;
+                last = q * (wave + 1) + (r * (wave + 1)) / nw;
+            } else {
+                wave_range(a.offsets, a.count, wave, nw, &first, &last);
+            }
             for (uint64_t p = first; p < last; p++) one(p);
         }
         if constexpr (RPC && VERIFY) rpc_add_counts<kCounts>(a.mismatches);

@@ -436,10 +436,13 @@ struct KernelKey {
     int width, lg, mode, op;
     bool nt, light, split;
     MsgFrame frame = kFramePayloads;
+    // the message side by address list (the _rpc_message_list calls): message p is the len[p] bytes at address
+    // addr[p], where the table form has buf[off[p], off[p + 1]).  Twins of the RPC frame's kernels, no others.
+    bool list = false;
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split && a.frame == b.frame;
+           a.split == b.split && a.frame == b.frame && a.list == b.list;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -448,6 +451,7 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
     if ((k.width != 32 && k.width != 64) || k.lg < 0 || k.lg > CRC_GPU_MAX_LOG2G) return false;
     if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
     const bool checks = k.op == kOpVerify || k.op == kOpSeal, copies = k.op == kOpPack || k.op == kOpUnpack;
+    if (k.list && k.frame != kFrameRpc) return false;  // the list form: of whole RPC messages only (all twelve)
     switch (k.frame) {
         case kFramePayloads: break;
         // twins of the CRC-32C offsets kernels (light, full, non-temporal), never split: a detached verify or
@@ -481,8 +485,8 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
-inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, MsgFrame frame = kFramePayloads) {
-    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, frame == kFrameInPlace ? kFramePayloads : frame};
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, MsgFrame frame = kFramePayloads, bool list = false) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, frame == kFrameInPlace ? kFramePayloads : frame, list};
     if (p.split) k.width = 64, k.lg = CRC_GPU_MAX_LOG2G, k.mode = kFixedAligned, k.light = false;
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;

@@ -341,11 +341,11 @@ struct KLaunch {
 };
 
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
-template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, MsgFrame FRAME>
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, MsgFrame FRAME, bool LIST>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, FRAME})) {
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, FRAME, LIST})) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
-        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, FRAME>, S::block, S::blocks_per_cu};
+        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, FRAME, LIST>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
     return {};
@@ -371,8 +371,10 @@ KLaunch kernel_for(const KernelKey &k) {
                         return lift<2>(k.light, [&](auto light) {
                             return lift<2>(k.split, [&](auto split) {
                                 return lift<kFrameRpc + 1>(k.frame, [&](auto frame) {
-                                    return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
-                                                      split() != 0, (MsgFrame)frame()>();
+                                    return lift<2>(k.list, [&](auto list) {
+                                        return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
+                                                          split() != 0, (MsgFrame)frame(), list() != 0>();
+                                    });
                                 });
                             });
                         });
@@ -467,7 +469,7 @@ int offsets_call(const OffsetsCall &c) {
     if (c.count == 0) return MCHECKSUM_GPU_OK;
     if (in_place && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const KLaunch k = kernel_for(kernel_key(p, c.op, c.frame));
+    const KLaunch k = kernel_for(kernel_key(p, c.op, c.frame, c.list));
     if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     BatchArgs a = batch_args_of(c, pack, shift, hdr_pack, m.msb, error_word());
     SlotRef sr;
@@ -1126,6 +1128,82 @@ int mchecksum_gpu_pack_rpc_messages(const char *header_method, const char *paylo
     c.hdr_method = header_method;
     c.dst = dev_buf;
     c.dst_off = dev_msg_offsets;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+// The four RPC calls with the message side by address list: the addresses ride where the message table does, with
+// no buffer under them (offsets_call.h: OffsetsCall::list, msg_len).
+int mchecksum_gpu_verify_rpc_message_list(const char *header_method, const char *payload_method, int kind,
+                                          const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                          size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+                                          uint32_t *dev_counts, void *stream) {
+    OffsetsCall c{kOpVerify, payload_method, nullptr, dev_msg_addr, count};
+    c.frame = kFrameRpc;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.list = true;
+    c.msg_len = dev_msg_len;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_counts;  // the six class counts
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_seal_rpc_message_list(const char *header_method, const char *payload_method, int kind,
+                                        const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                        size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
+    OffsetsCall c{kOpSeal, payload_method, nullptr, dev_msg_addr, count};  // (no `out`: the addresses are written through)
+    c.frame = kFrameRpc;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.list = true;
+    c.msg_len = dev_msg_len;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_unpack_rpc_message_list(const char *header_method, const char *payload_method, int kind,
+                                          const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                          size_t payload_offset, size_t hash_offset, void *dev_dst,
+                                          const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_counts,
+                                          void *stream) {
+    OffsetsCall c{kOpUnpack, payload_method, nullptr, dev_msg_addr, count};
+    c.frame = kFrameRpc;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.list = true;
+    c.msg_len = dev_msg_len;
+    c.dst = dev_dst;
+    c.dst_off = dev_dst_offsets;
+    c.pay_off = payload_offset;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_counts;  // the seven class counts
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_pack_rpc_message_list(const char *header_method, const char *payload_method, int kind,
+                                        const void *dev_src, const uint64_t *dev_src_offsets,
+                                        const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                        size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
+    // the list is the written side: the headers (and their flags) are read through it, the source stays a table
+    OffsetsCall c{kOpPack, payload_method, dev_src, dev_src_offsets, count};
+    c.frame = kFrameRpc;
+    c.kind = kind;
+    c.hdr_method = header_method;
+    c.list = true;
+    c.msg_len = dev_msg_len;
+    c.dst_off = dev_msg_addr;
     c.pay_off = payload_offset;
     c.hash_off = hash_offset;
     c.status = dev_status;

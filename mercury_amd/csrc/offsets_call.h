@@ -39,6 +39,10 @@ struct OffsetsCall {
     // messages at src, a pack's at dst.
     int kind = 0;
     const char *hdr_method = nullptr;
+    // kFrameRpc by address list: the message side -- src_off, a pack's dst_off -- holds `count` absolute addresses
+    // and msg_len their lengths; that side's buffer pointer (src, a pack's dst, a seal's out) is null
+    bool list = false;
+    const uint64_t *msg_len = nullptr;
 };
 
 constexpr bool op_copies(BatchOp op) { return op == kOpPack || op == kOpUnpack; }
@@ -46,19 +50,24 @@ constexpr bool op_copies(BatchOp op) { return op == kOpPack || op == kOpUnpack; 
 // What a non-empty call must supply besides src and src_off, and whether its
 // method is checked ahead of the device, as an argument (the calls on HG and
 // RPC messages but verify_messages; as verify_core_headers does) or after it.
+// A list call needs its lengths, and no buffer for its message side: src_buf and dst_buf say which of the
+// two buffer pointers a call still needs (both, but for a list), and a list seal writes through its addresses.
 struct OffsetsNeeds {
     bool out, dst, hdr, expected, method_first;
+    bool msg_len = false, src_buf = true, dst_buf = true;
 };
-constexpr OffsetsNeeds offsets_needs(BatchOp op, MsgFrame frame) {
-    return {op == kOpChecksum || op == kOpUpdate || (op == kOpSeal && frame != kFrameDetached),  // values or hashes stored
+constexpr OffsetsNeeds offsets_needs(BatchOp op, MsgFrame frame, bool list = false) {
+    return {op == kOpChecksum || op == kOpUpdate || (op == kOpSeal && frame != kFrameDetached && !list),  // values or hashes stored
             op_copies(op), frame == kFrameDetached, op == kOpVerify && frame == kFramePayloads,
-            op_copies(op) || op == kOpSeal || frame == kFrameDetached || frame == kFrameRpc};
+            op_copies(op) || op == kOpSeal || frame == kFrameDetached || frame == kFrameRpc,
+            list, !list || op == kOpPack, !list || op != kOpPack};
 }
 // Whether a call lacks a pointer it must supply: an empty batch needs no buffers (not even the one-entry table).
 inline bool offsets_lacks_pointer(const OffsetsCall &c) {
-    const OffsetsNeeds need = offsets_needs(c.op, c.frame);
-    return c.count && (!c.src || !c.src_off || (need.out && !c.out) || (need.dst && (!c.dst || !c.dst_off)) ||
-                       (need.hdr && (!c.hdr || !c.hdr_off)) || (need.expected && !c.expected));
+    const OffsetsNeeds need = offsets_needs(c.op, c.frame, c.list);
+    return c.count && ((need.src_buf && !c.src) || !c.src_off || (need.out && !c.out) ||
+                       (need.dst && ((need.dst_buf && !c.dst) || !c.dst_off)) || (need.hdr && (!c.hdr || !c.hdr_off)) ||
+                       (need.expected && !c.expected) || (need.msg_len && !c.msg_len));
 }
 
 // The kernels' argument of a call: pack = the model's table pack, shift = its
@@ -84,6 +93,13 @@ inline BatchArgs batch_args_of(const OffsetsCall &c, const void *pack, const voi
         else a.expected = c.expected;
     }
     if (c.frame == kFrameRpc) a.set_rpc_pay_off(c.pay_off);
+    if (c.list) {
+        // the list's entries are whole addresses: the kernels add them to a null buffer pointer, whatever the call holds
+        a.set_rpc_list_len(c.msg_len);
+        if (c.op == kOpPack) a.copy_dst = nullptr;
+        else a.base = nullptr;
+        if (c.op == kOpSeal) a.msgs = nullptr;
+    }
     a.status = c.status;
     a.mismatches = c.mismatches;
     a.pack = pack;

@@ -889,6 +889,185 @@ def pack_rpc_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: torch.
     return status
 
 
+def rpc_message_list(parts, device=None, with_host: bool = False):
+    """The two arrays of the *_rpc_message_list calls from a list of
+    (tensor, start, length): message i is the `length` bytes `start` bytes into
+    `tensor` (a contiguous device tensor; its data_ptr() is the allocation's
+    address), in the order given -- any tensors, any order, gaps as they come.
+    Returns (msg_addr, msg_len), device int64 tensors; with_host=True also the
+    two host arrays (numpy uint64), for the wrappers' overlap checks.  The
+    tensors in `parts` must stay alive while the arrays are in use: the arrays
+    hold addresses, not references."""
+    import numpy as np
+    addr, lens = np.zeros(len(parts), dtype=np.uint64), np.zeros(len(parts), dtype=np.uint64)
+    for i, (t, start, length) in enumerate(parts):
+        _check_device_u8(t, f"parts[{i}][0]")
+        if device is None:
+            device = t.device
+        if t.device != device:
+            raise GpuChecksumError(f"parts[{i}] lies on {t.device}, the list on {device}")
+        if start < 0 or length < 0 or start + length > t.numel() * t.element_size():
+            raise GpuChecksumError(f"parts[{i}] extends past the end of its tensor")
+        addr[i], lens[i] = t.data_ptr() + start, length
+    if device is None:
+        raise GpuChecksumError("an empty list needs a device")
+    dev = (torch.from_numpy(addr.view(np.int64)).to(device), torch.from_numpy(lens.view(np.int64)).to(device))
+    return dev + (addr, lens) if with_host else dev
+
+
+def _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind: str, payload_offset: int, hash_offset: int,
+                    written: bool):
+    """The message side of an RPC message-list call; returns (count, the kind's
+    number).  With both host arrays, messages that are written must not overlap
+    one another."""
+    from ._lib import CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE
+    _check_i64_table(msg_addr, "msg_addr")
+    count = msg_addr.numel()
+    _check_i64_table(msg_len, "msg_len", count)
+    if msg_len.numel() != count:
+        raise GpuChecksumError("msg_addr and msg_len need the same number of entries")
+    k = {"request": CORE_HEADER_REQUEST, "response": CORE_HEADER_RESPONSE}.get(kind)
+    if k is None:
+        raise GpuChecksumError('kind must be "request" or "response"')
+    if hash_offset < 16 or hash_offset > 1 << 30 or hash_offset + 4 > payload_offset:
+        raise GpuChecksumError("hash_offset must lie in 16..2^30 and hash_offset + 4 must not exceed payload_offset")
+    if (addr_host is None) != (len_host is None):
+        raise GpuChecksumError("addr_host and len_host go together")
+    if addr_host is not None:
+        import numpy as np
+        ah, lh = np.asarray(addr_host, dtype=np.uint64), np.asarray(len_host, dtype=np.uint64)
+        if len(ah) != count or len(lh) != count:
+            raise GpuChecksumError("addr_host / len_host do not match msg_addr / msg_len")
+        if written and count > 1:
+            order = np.argsort(ah, kind="stable")
+            a, n = ah[order], lh[order]
+            if np.any((a[:-1] + n[:-1] > a[1:]) & (n[:-1] > 0) & (n[1:] > 0)):
+                raise GpuChecksumError("messages that are written overlap one another")
+    return count, k
+
+
+def _check_rpc_list_copy(addr_host, len_host, count, other, other_offsets, other_host, names):
+    """The table side of a copying RPC message-list call (_check_rpc_copy's
+    checks): with all host copies, no message may overlap the other range."""
+    _check_device_u8(other, names[0])
+    _check_offsets(other, other_offsets, other_host)
+    if other_offsets.numel() != count + 1:
+        raise GpuChecksumError(f"{names[1]} needs one entry more than msg_addr")
+    if addr_host is not None and other_host is not None and count:
+        import numpy as np
+        ah, lh = np.asarray(addr_host, dtype=np.uint64), np.asarray(len_host, dtype=np.uint64)
+        oo = np.asarray(other_host, dtype=np.uint64)
+        o0, o1 = other.data_ptr() + int(oo[0]), other.data_ptr() + int(oo[-1])
+        if o1 > o0 and np.any((lh > 0) & (ah < np.uint64(o1)) & (ah + lh > np.uint64(o0))):
+            raise GpuChecksumError(f"a message and the {names[0]} range overlap")
+
+
+def _rpc_counts(counts, classes: int, device):
+    if counts is None:
+        return torch.zeros(classes, dtype=torch.int32, device=device)
+    if counts is not False and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32
+                                or not counts.is_cuda or not counts.is_contiguous() or counts.numel() < classes):
+        raise GpuChecksumError(f"counts must be a contiguous device int32 tensor of at least {classes} elements")
+    return counts
+
+
+def verify_rpc_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, kind: str = "request",
+                            payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                            method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None,
+                            counts=None):
+    """verify_rpc_messages with the messages addressed by a list
+    (mchecksum_gpu_verify_rpc_message_list): message i is the msg_len[i] bytes at
+    the device address msg_addr[i] (device int64 tensors, rpc_message_list
+    builds them) -- in any number of allocations, in any order, with any gaps.
+    Rules, statuses and counts are verify_rpc_messages'; returns (status, counts).
+    A message shorter than 16 bytes is RPC_SHORT and its address is not used."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, False)
+    status = _rpc_status(msg_addr, count, status)
+    counts = _rpc_counts(counts, RPC_CLASSES, msg_addr.device)
+    _same_device(msg_addr, msg_len=msg_len, status=None if status is False else status,
+                 counts=None if counts is False else counts)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_verify_rpc_message_list(header_method.encode(), method.encode(), k,
+                                                          msg_addr.data_ptr(), msg_len.data_ptr(), count,
+                                                          payload_offset, hash_offset, _ptr(status), _ptr(counts),
+                                                          _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_rpc_message_list")
+    return status, counts
+
+
+def seal_rpc_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, kind: str = "request",
+                          payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                          method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None):
+    """seal_rpc_messages with the messages addressed by a list
+    (mchecksum_gpu_seal_rpc_message_list), written through their addresses: the
+    same 2 or 6 bytes of a message, no others.  The messages must not overlap
+    one another; with both host arrays given that is checked here.  Returns
+    status as seal_rpc_messages does."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, True)
+    status = _rpc_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_seal_rpc_message_list(header_method.encode(), method.encode(), k,
+                                                        msg_addr.data_ptr(), msg_len.data_ptr(), count,
+                                                        payload_offset, hash_offset, _ptr(status),
+                                                        _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_rpc_message_list")
+    return status
+
+
+def unpack_rpc_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, dst: torch.Tensor,
+                            dst_offsets: torch.Tensor, kind: str = "request", payload_offset: int = 20,
+                            hash_offset: int = 16, header_method: str = "crc16", method: str = "crc32c", stream=None,
+                            addr_host=None, len_host=None, dst_offsets_host=None, status=None, counts=None):
+    """unpack_rpc_messages with the messages addressed by a list
+    (mchecksum_gpu_unpack_rpc_message_list); the destination stays
+    dst[dst_offsets[i] : dst_offsets[i+1]].  Rules, statuses, counts and what is
+    written are unpack_rpc_messages'; returns (status, counts).  No message may
+    overlap `dst`; with all three host copies given that is checked here."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, False)
+    _check_rpc_list_copy(addr_host, len_host, count, dst, dst_offsets, dst_offsets_host, ("dst", "dst_offsets"))
+    status = _rpc_status(msg_addr, count, status)
+    counts = _rpc_counts(counts, RPC_COPY_CLASSES, msg_addr.device)
+    _same_device(msg_addr, msg_len=msg_len, dst=dst, dst_offsets=dst_offsets,
+                 status=None if status is False else status, counts=None if counts is False else counts)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_unpack_rpc_message_list(header_method.encode(), method.encode(), k,
+                                                          msg_addr.data_ptr(), msg_len.data_ptr(), count,
+                                                          payload_offset, hash_offset, dst.data_ptr(),
+                                                          dst_offsets.data_ptr(), _ptr(status), _ptr(counts),
+                                                          _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_rpc_message_list")
+    return status, counts
+
+
+def pack_rpc_message_list(src: torch.Tensor, src_offsets: torch.Tensor, msg_addr: torch.Tensor,
+                          msg_len: torch.Tensor, kind: str = "request", payload_offset: int = 20,
+                          hash_offset: int = 16, header_method: str = "crc16", method: str = "crc32c", stream=None,
+                          src_offsets_host=None, addr_host=None, len_host=None, status=None):
+    """pack_rpc_messages with the messages addressed by a list
+    (mchecksum_gpu_pack_rpc_message_list): the headers are read and the
+    payloads and hashes written through the addresses; the source stays
+    src[src_offsets[i] : src_offsets[i+1]].  Rules, statuses and what is written
+    are pack_rpc_messages'; returns status.  The messages must not overlap one
+    another or `src`; with the host copies given that is checked here."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, True)
+    _check_rpc_list_copy(addr_host, len_host, count, src, src_offsets, src_offsets_host, ("src", "src_offsets"))
+    status = _rpc_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, src=src, src_offsets=src_offsets,
+                 status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_pack_rpc_message_list(header_method.encode(), method.encode(), k, src.data_ptr(),
+                                                        src_offsets.data_ptr(), msg_addr.data_ptr(),
+                                                        msg_len.data_ptr(), count, payload_offset, hash_offset,
+                                                        _ptr(status), _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_rpc_message_list")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its
