@@ -497,6 +497,72 @@ mchecksum_gpu_state_seal_messages(const char *hash_method,
     const uint64_t *dev_msg_offsets, size_t hash_offset, uint8_t *dev_status,
     void *stream);
 
+/* The four calls above with BOTH sides addressed by lists: what Mercury holds
+ * of overflow RPCs.  The eager messages are those of a drain (one address and
+ * one length per completion, as mchecksum_gpu_verify_rpc_message_list takes
+ * them), and every payload is an allocation of its own: hg_get_extra_payload
+ * allocates one page-aligned extra buffer per handle (src/mercury.c:933-934),
+ * and so does the sender's out_extra_buf.  A base pointer and a table of
+ * non-decreasing offsets cannot name either.
+ *
+ * All four arrays are device-resident and hold `count` entries each (not
+ * count + 1).  Everything not said here is the table call's of the same name,
+ * by reference: statuses 0 / 1, the mismatch counter, the methods, the
+ * argument bounds and their order (EINVAL -- each array is a required pointer
+ * with count > 0 --, then the method's EMETHOD ahead of the device, then
+ * ENODEV; count == 0 needs no buffers but passes the checks first), and the
+ * launch, capture and fail-closed rules (a replay reads the current contents
+ * of all four arrays).  What follows from entries that lie anywhere:
+ *
+ * Message side.  Message i is the L = dev_msg_len[i] bytes at the device
+ * address dev_msg_addr[i]; an end that wraps the address space gives L = 0.
+ * Its slot exists iff L >= hash_offset + 4, and is the 4 bytes at
+ * dev_msg_addr[i] + hash_offset, read or written byte by byte at any
+ * alignment.  A message without a slot is never dereferenced and its address
+ * may be NULL: a verify counts it as a mismatch with status 1, a seal gives
+ * status 1 and makes no store.  A seal writes exactly those 4 bytes per entry
+ * and nothing else; slots that are written must not overlap one another.
+ *
+ * Payload side.  Payload i is the N = dev_payload_len[i] bytes at the device
+ * address dev_payload_addr[i].  A payload whose end wraps the address space
+ * fails its entry -- status 1, a mismatch on verify, no store on seal -- and
+ * nothing of it is read.  N = 0 is a legitimate payload: its CRC is the
+ * model's value of the empty message, compared or stored as any other, and
+ * its address is never dereferenced and may be NULL.  Reads: per payload, in
+ * aligned 16-byte pieces that stay inside the aligned 128-byte lines holding
+ * its first and its last byte -- a payload inside any device allocation
+ * satisfies this, a page-aligned extra buffer certainly --, and nothing
+ * between, before or behind payloads enters a value.
+ *
+ * The two state calls end a streamed transfer whose update_segments calls took
+ * the payloads by address already (dev_seg_addr / dev_seg_len).  DESIGN.md
+ * 4.26 has the design and the measurements against the table calls. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_detached_message_list(const char *hash_method,
+    const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len,
+    size_t hash_offset, const uint64_t *dev_payload_addr,
+    const uint64_t *dev_payload_len, size_t count, uint8_t *dev_status,
+    uint32_t *dev_mismatches, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_detached_message_list(const char *hash_method,
+    const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len,
+    size_t hash_offset, const uint64_t *dev_payload_addr,
+    const uint64_t *dev_payload_len, size_t count, uint8_t *dev_status,
+    void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_verify_message_list(const char *hash_method,
+    const void *dev_state, size_t count, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t hash_offset, uint8_t *dev_status,
+    uint32_t *dev_mismatches, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_state_seal_message_list(const char *hash_method,
+    const void *dev_state, size_t count, const uint64_t *dev_msg_addr,
+    const uint64_t *dev_msg_len, size_t hash_offset, uint8_t *dev_status,
+    void *stream);
+
 /* Pack, hash and seal in one pass over the payload bytes.  Payload i =
  * dev_src[dev_src_offsets[i], dev_src_offsets[i+1]) (the checksum_offsets
  * layout: any start byte, readable to the next 16-byte boundary) is copied to
@@ -1038,9 +1104,9 @@ mchecksum_gpu_pack_rpc_messages(const char *header_method,
  * an eager one shorter than payload_offset or -- unpack, pack -- one that
  * does not fit.  Nothing outside the messages and the other range is written.
  * DESIGN.md 4.25 has the design and the measurements against the table calls.
- * Not yet: the DEFERRED messages of a list cannot go to
- * mchecksum_gpu_verify_detached_messages as they are (it reads its slots
- * through a table). */
+ * The DEFERRED messages of a list go on to
+ * mchecksum_gpu_verify_detached_message_list as they are: a sub-list of the
+ * same two arrays. */
 MCHECKSUM_PUBLIC int
 mchecksum_gpu_verify_rpc_message_list(const char *header_method,
     const char *payload_method, int kind, const uint64_t *dev_msg_addr,

@@ -41,7 +41,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_seal_rpc_messages", "mchecksum_gpu_unpack_rpc_messages",
                "mchecksum_gpu_pack_rpc_messages", "mchecksum_gpu_verify_rpc_message_list",
                "mchecksum_gpu_seal_rpc_message_list", "mchecksum_gpu_unpack_rpc_message_list",
-               "mchecksum_gpu_pack_rpc_message_list")
+               "mchecksum_gpu_pack_rpc_message_list", "mchecksum_gpu_verify_detached_message_list",
+               "mchecksum_gpu_seal_detached_message_list", "mchecksum_gpu_state_verify_message_list",
+               "mchecksum_gpu_state_seal_message_list")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -221,6 +223,19 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_unpack_rpc_message_list.restype = c_int
     L.mchecksum_gpu_pack_rpc_message_list.argtypes = L.mchecksum_gpu_pack_rpc_messages.argtypes
     L.mchecksum_gpu_pack_rpc_message_list.restype = c_int
+    # the detached calls with both sides by address list: four device arrays of `count` entries
+    L.mchecksum_gpu_verify_detached_message_list.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                             c_size_t, c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_verify_detached_message_list.restype = c_int
+    L.mchecksum_gpu_seal_detached_message_list.argtypes = [c_char_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                           c_size_t, c_void_p, c_void_p]
+    L.mchecksum_gpu_seal_detached_message_list.restype = c_int
+    L.mchecksum_gpu_state_verify_message_list.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                          c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_state_verify_message_list.restype = c_int
+    L.mchecksum_gpu_state_seal_message_list.argtypes = [c_char_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                        c_void_p, c_void_p]
+    L.mchecksum_gpu_state_seal_message_list.restype = c_int
     L.mchecksum_gpu_pack_messages.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
                                               c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_pack_messages.restype = c_int

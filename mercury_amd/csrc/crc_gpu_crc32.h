@@ -448,9 +448,16 @@ __device__ __forceinline__ void rpc_fail_closed(const BatchArgs &a) {
 // whose payload is not hashed runs the empty payload at address 0 -- no load,
 // where the table form's may read on in the line of the message's end --, and
 // the light layout deals messages by count, there being no table to balance by.
-template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, mck::MsgFrame FRAME = mck::kFramePayloads, bool LIST = false>
+// BOTH (KernelKey::both_lists; kFrameDetached only): both sides are address
+// lists -- the payloads' as above, and the slots' table entry p is the eager
+// message's address, used with a null `msgs`, its length from a third array
+// (BatchArgs::slot_list_len).  The rules of entries that lie anywhere are
+// launch_plan.h's (list_msg_len, list_payload_ok, _len, _at).
+template <int LOG2G, int MODE, int OP, bool NT, bool LIGHT = false, mck::MsgFrame FRAME = mck::kFramePayloads, bool LIST = false,
+          bool BOTH = false>
 __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArgs a) {
-    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, FRAME, LIST}), "no such batch kernel");
+    static_assert(mck::kernel_key_valid(mck::KernelKey{32, LOG2G, MODE, OP, NT, LIGHT, false, FRAME, LIST, BOTH}),
+                  "no such batch kernel");
     // (enumerators: as constexpr locals, their debug records moved instructions in a -g build of one kernel)
     enum : bool {
         VERIFY = OP == mck::kOpVerify || OP == mck::kOpUnpack,
@@ -458,7 +465,7 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
         SEAL = OP == mck::kOpSeal || OP == mck::kOpPack,
         COPY = OP == mck::kOpPack || OP == mck::kOpUnpack,
         RPC = FRAME == mck::kFrameRpc,
-        LIST_BATCH = LIST && !(COPY && SEAL)  // the list is the batch's own side (a pack's is the written side)
+        LIST_BATCH = (LIST && !(COPY && SEAL)) || BOTH  // the list is the batch's own side (a pack's is the written side)
     };
     constexpr int kWavesPerBlock = kBlk32<LIGHT> / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LIGHT ? kL32LightBytes : kL32Bytes];
@@ -612,11 +619,24 @@ __global__ __launch_bounds__(kBlk32<LIGHT>, 1) void crc32c_batch_kernel(BatchArg
                 // four bytes at any alignment -- the in-place epilogues below at
                 // another address (launch_plan.h: msg_slot_ok, msg_slot_at).  A
                 // verify reads msgs only.
-                const uint64_t h0 = a.dst_offsets[p], h1 = a.dst_offsets[p + 1], n = m1 - m0;
-                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + m0, n, gl, lc0, lc1)
-                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + m0, n, gl, lc0, lc1);
+                // BOTH: m1 - m0 is the payload's length whether its end wraps or not; a
+                // wrapped payload is hashed as an empty one and fails its entry with the
+                // slotless messages, and every empty payload runs at address 0.
+                const uint64_t h0 = a.dst_offsets[p];
+                uint64_t h1, n = m1 - m0, o = m0;
+                [[maybe_unused]] bool wrapped = false;
+                if constexpr (BOTH) {
+                    h1 = h0 + mck::list_msg_len(h0, a.slot_list_len()[p]);
+                    wrapped = !mck::list_payload_ok(m0, n);
+                    o = mck::list_payload_at(m0, n);
+                    n = mck::list_payload_len(m0, n);
+                } else {
+                    h1 = a.dst_offsets[p + 1];
+                }
+                const uint32_t x = n < (1ull << 31) ? payload32_g64<NT>(lds, pk, a.base + o, n, gl, lc0, lc1)
+                                                    : payload32_generic<LOG2G, NT>(lds, pk, a.base + o, n, gl, lc0, lc1);
                 if (gl == 0) {
-                    const bool short_msg = !mck::msg_slot_ok(h0, h1, a.hash_off);
+                    const bool short_msg = !mck::msg_slot_ok(h0, h1, a.hash_off) || (BOTH && wrapped);
                     uint8_t *slot = a.msgs + mck::msg_slot_at(h0, a.hash_off);
                     if constexpr (SEAL) {
                         if (!short_msg) store_be32(slot, x ^ xorout);

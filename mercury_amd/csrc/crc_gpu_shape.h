@@ -105,6 +105,10 @@ struct BatchArgs {
     // offsets-mode kernel has a stride.  (An accessor, for the reason below.)
     MCK_HOST_DEVICE const uint64_t *rpc_list_len() const { return reinterpret_cast<const uint64_t *>(stride); }
     MCK_HOST_DEVICE void set_rpc_list_len(const uint64_t *v) { stride = reinterpret_cast<uint64_t>(v); }
+    // The detached calls with both sides by list (kFrameDetached, KernelKey::both_lists) carry the PAYLOADS' lengths
+    // there, and the eager messages' lengths in `len`'s place -- a detached call has no fixed length.
+    MCK_HOST_DEVICE const uint64_t *slot_list_len() const { return reinterpret_cast<const uint64_t *>(len); }
+    MCK_HOST_DEVICE void set_slot_list_len(const uint64_t *v) { len = reinterpret_cast<uint64_t>(v); }
     uint64_t len;  // fixed batches: bytes per payload
     // whole RPC messages (kFrameRpc): payload_offset in 64 bits, in `len`'s place.  (An accessor, not a member of a
     // union as below: a union here moved an instruction in every fixed generic CRC-32C kernel.)

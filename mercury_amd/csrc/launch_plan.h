@@ -293,6 +293,23 @@ MCK_HOST_DEVICE_INLINE uint64_t msg_slot_at(uint64_t m0, uint64_t hash_off) { re
 // hash_offset is carried in 32 bits (BatchArgs::hash_off), capped as payload_offset is
 constexpr uint64_t kMaxHashOff = 1ull << 30;
 
+// The detached calls with both sides by address list (the _detached_message_list
+// and _state_*_message_list calls): entry i is `len` bytes at `addr`, anywhere.
+// An eager message whose end wraps the address space holds no bytes -- its slot
+// rule is then msg_slot_ok(addr, addr + list_msg_len(addr, len), hash_off),
+// never true of an empty message, so a message without its slot is never
+// dereferenced and its address may be NULL.
+MCK_HOST_DEVICE_INLINE uint64_t list_msg_len(uint64_t addr, uint64_t len) { return addr + len >= addr ? len : 0; }
+// A payload whose end wraps fails its entry (status 1; a verify's mismatch, no
+// store of a seal) and none of it is read: the wave hashes list_payload_len bytes
+// at list_payload_at.  The empty payload -- a legitimate one too, whose CRC is
+// compared or stored as any other -- runs at address 0, where the
+// one-payload-per-wave window has no step (crc_gpu_window.h): its own address is
+// never dereferenced and may be NULL.
+MCK_HOST_DEVICE_INLINE bool list_payload_ok(uint64_t addr, uint64_t len) { return addr + len >= addr; }
+MCK_HOST_DEVICE_INLINE uint64_t list_payload_len(uint64_t addr, uint64_t len) { return list_payload_ok(addr, len) ? len : 0; }
+MCK_HOST_DEVICE_INLINE uint64_t list_payload_at(uint64_t addr, uint64_t len) { return list_payload_len(addr, len) ? addr : 0; }
+
 // ---- whole RPC messages: mchecksum_gpu_verify_rpc_messages, _seal_rpc_messages,
 // ---- and with the payload copied: _unpack_rpc_messages, _pack_rpc_messages ----
 //
@@ -439,10 +456,14 @@ struct KernelKey {
     // the message side by address list (the _rpc_message_list calls): message p is the len[p] bytes at address
     // addr[p], where the table form has buf[off[p], off[p + 1]).  Twins of the RPC frame's kernels, no others.
     bool list = false;
+    // both sides by address list (the _detached_message_list calls): payload p is the len[p] bytes at its
+    // address, and its slot lies in the eager message at an address with a length of its own.  Twins of the
+    // detached frame's six kernels, no others; never together with `list`, which names the RPC frame's.
+    bool both_lists = false;
 };
 constexpr bool operator==(const KernelKey &a, const KernelKey &b) {
     return a.width == b.width && a.lg == b.lg && a.mode == b.mode && a.op == b.op && a.nt == b.nt && a.light == b.light &&
-           a.split == b.split && a.frame == b.frame && a.list == b.list;
+           a.split == b.split && a.frame == b.frame && a.list == b.list && a.both_lists == b.both_lists;
 }
 
 // The instantiations there are -- kernel_for has exactly these, and each
@@ -452,6 +473,7 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
     if (k.light && (k.width != 32 || k.nt)) return false;  // light: CRC-32C only, and no non-temporal form
     const bool checks = k.op == kOpVerify || k.op == kOpSeal, copies = k.op == kOpPack || k.op == kOpUnpack;
     if (k.list && k.frame != kFrameRpc) return false;  // the list form: of whole RPC messages only (all twelve)
+    if (k.both_lists && (k.frame != kFrameDetached || k.list)) return false;  // of the detached frame only (all six)
     switch (k.frame) {
         case kFramePayloads: break;
         // twins of the CRC-32C offsets kernels (light, full, non-temporal), never split: a detached verify or
@@ -485,8 +507,10 @@ constexpr bool kernel_key_valid(const KernelKey &k) {
 
 // The kernel a plan launches for op.  A plan's fields say what the batch is
 // like; the key drops what the kernel in question has no form for.
-inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, MsgFrame frame = kFramePayloads, bool list = false) {
-    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, frame == kFrameInPlace ? kFramePayloads : frame, list};
+inline KernelKey kernel_key(const LaunchPlan &p, BatchOp op, MsgFrame frame = kFramePayloads, bool list = false,
+                            bool both_lists = false) {
+    KernelKey k{p.width, p.lg, p.mode, op, p.nt, p.light, p.split, frame == kFrameInPlace ? kFramePayloads : frame, list,
+                both_lists};
     if (p.split) k.width = 64, k.lg = CRC_GPU_MAX_LOG2G, k.mode = kFixedAligned, k.light = false;
     if (k.mode == kOffsets) k.lg = CRC_GPU_MAX_LOG2G;
     if (k.width != 32) k.light = false;

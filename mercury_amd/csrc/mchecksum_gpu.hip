@@ -341,11 +341,12 @@ struct KLaunch {
 };
 
 // The kernel of one key, if there is one (kernel_key_valid): only those are instantiated.
-template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, MsgFrame FRAME, bool LIST>
+template <int W, int LOG2G, int MODE, int OP, bool NT, bool LIGHT, bool SPLIT, MsgFrame FRAME, bool LIST, bool BOTH>
 KLaunch kernel_ptr() {
-    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, FRAME, LIST})) {
+    if constexpr (kernel_key_valid(KernelKey{W, LOG2G, MODE, OP, NT, LIGHT, SPLIT, FRAME, LIST, BOTH})) {
         using S = Shape<W, MODE, LIGHT, LOG2G>;
-        if constexpr (W == 32) return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, FRAME, LIST>, S::block, S::blocks_per_cu};
+        if constexpr (W == 32)
+            return {crc32c_batch_kernel<LOG2G, MODE, OP, NT, LIGHT, FRAME, LIST, BOTH>, S::block, S::blocks_per_cu};
         else return {crc64_batch_kernel<LOG2G, MODE, OP, NT, SPLIT>, S::block, S::blocks_per_cu};
     }
     return {};
@@ -372,8 +373,10 @@ KLaunch kernel_for(const KernelKey &k) {
                             return lift<2>(k.split, [&](auto split) {
                                 return lift<kFrameRpc + 1>(k.frame, [&](auto frame) {
                                     return lift<2>(k.list, [&](auto list) {
-                                        return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
-                                                          split() != 0, (MsgFrame)frame(), list() != 0>();
+                                        return lift<2>(k.both_lists, [&](auto both) {
+                                            return kernel_ptr<w64() ? 64 : 32, lg(), mode(), op(), nt() != 0, light() != 0,
+                                                              split() != 0, (MsgFrame)frame(), list() != 0, both() != 0>();
+                                        });
                                     });
                                 });
                             });
@@ -469,7 +472,7 @@ int offsets_call(const OffsetsCall &c) {
     if (c.count == 0) return MCHECKSUM_GPU_OK;
     if (in_place && m.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD, "message verify carries a 32-bit header hash: crc32c only");
-    const KLaunch k = kernel_for(kernel_key(p, c.op, c.frame, c.list));
+    const KLaunch k = kernel_for(kernel_key(p, c.op, c.frame, c.list, c.both_lists));
     if (!k.k) return set_err(MCHECKSUM_GPU_EINVAL, "no batch kernel for this call");
     BatchArgs a = batch_args_of(c, pack, shift, hdr_pack, m.msb, error_word());
     SlotRef sr;
@@ -606,6 +609,7 @@ __global__ __launch_bounds__(256) void state_verify_kernel(const T *st, const T 
 // push of overflow payloads.  The slot rule is the detached kernels'
 // (launch_plan.h: msg_slot_ok, msg_slot_at); 32-bit models only, all of them
 // reflected, so the value is the register ^ xorout.  The states are only read.
+// (state_message_list_kernel below: the same element with the slot by address and length.)
 template <bool SEAL>
 __global__ __launch_bounds__(256) void state_messages_kernel(const uint32_t *st, uint64_t n, uint32_t xorout, uint8_t *msgs,
                                                              const uint64_t *msg_off, uint32_t hash_off, uint8_t *status,
@@ -615,6 +619,29 @@ __global__ __launch_bounds__(256) void state_messages_kernel(const uint32_t *st,
         const uint64_t m0 = msg_off[i], m1 = msg_off[i + 1];
         const bool short_msg = !mck::msg_slot_ok(m0, m1, hash_off);
         uint8_t *slot = msgs + mck::msg_slot_at(m0, hash_off);
+        const uint32_t v = mck_reg_to_crc32(st[i], xorout, 0);
+        if constexpr (SEAL) {
+            if (!short_msg) store_be32(slot, v);
+            if (status) status[i] = short_msg ? 1 : 0;
+        } else {
+            nbad += mck::seg_verify_decide(short_msg, v, short_msg ? 0 : load_be32(slot), status, i);
+        }
+    }
+    if constexpr (!SEAL) add_mismatches(mism, nbad);  // once per workgroup (crc_gpu_common.h)
+}
+
+// state_messages_kernel with the eager messages by address list: message i is the msg_len[i] bytes at msg_addr[i],
+// anywhere, and an end that wraps the address space an empty message (launch_plan.h: list_msg_len).  A message
+// without its slot is never dereferenced.
+template <bool SEAL>
+__global__ __launch_bounds__(256) void state_message_list_kernel(const uint32_t *st, uint64_t n, uint32_t xorout,
+                                                                 const uint64_t *msg_addr, const uint64_t *msg_len,
+                                                                 uint32_t hash_off, uint8_t *status, uint32_t *mism) {
+    uint32_t nbad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t m0 = msg_addr[i], m1 = m0 + mck::list_msg_len(m0, msg_len[i]);
+        const bool short_msg = !mck::msg_slot_ok(m0, m1, hash_off);
+        uint8_t *slot = reinterpret_cast<uint8_t *>(mck::msg_slot_at(m0, hash_off));
         const uint32_t v = mck_reg_to_crc32(st[i], xorout, 0);
         if constexpr (SEAL) {
             if (!short_msg) store_be32(slot, v);
@@ -828,9 +855,13 @@ int state_call(const char *method, size_t count, Model *m, crc_rmodel_t *rm, Dev
 // (a 32-bit model, ahead of the device, as the calls on HG messages check
 // it), then the device.  An element kernel: no work-queue slot, no workspace,
 // no device-side wait.
+// dev_msg_len: the list form -- dev_msg_offsets holds `count` addresses with no buffer under them, dev_msg_len
+// their lengths.
 int state_messages_call(bool seal, const char *method, const void *dev_state, size_t count, void *dev_msgs,
-                        const uint64_t *dev_msg_offsets, size_t hash_off, uint8_t *status, uint32_t *mism, void *stream) {
-    if (count && (!dev_state || !dev_msgs || !dev_msg_offsets)) return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+                        const uint64_t *dev_msg_offsets, size_t hash_off, uint8_t *status, uint32_t *mism, void *stream,
+                        bool list = false, const uint64_t *dev_msg_len = nullptr) {
+    if (count && (!dev_state || !dev_msg_offsets || (list ? !dev_msg_len : !dev_msgs)))
+        return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (hash_off > kMaxHashOff) return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must not exceed 2^30");
     if ((uint64_t)count > kMaxUnits) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 payloads in one call");
     Model m;
@@ -844,9 +875,13 @@ int state_messages_call(bool seal, const char *method, const void *dev_state, si
     if (count == 0) return MCHECKSUM_GPU_OK;
     const crc_rmodel_t rm = gpu_rmodel(m.idx);
     const dim3 grid(elem_grid(count)), block(256);
-    const hipError_t e = launch_kernel(seal ? state_messages_kernel<true> : state_messages_kernel<false>, grid, block,
-                                       (hipStream_t)stream, nullptr, (const uint32_t *)dev_state, (uint64_t)count,
-                                       (uint32_t)rm.xorout, (uint8_t *)dev_msgs, dev_msg_offsets, (uint32_t)hash_off, status, mism);
+    const hipError_t e =
+        list ? launch_kernel(seal ? state_message_list_kernel<true> : state_message_list_kernel<false>, grid, block,
+                             (hipStream_t)stream, nullptr, (const uint32_t *)dev_state, (uint64_t)count, (uint32_t)rm.xorout,
+                             dev_msg_offsets, dev_msg_len, (uint32_t)hash_off, status, mism)
+             : launch_kernel(seal ? state_messages_kernel<true> : state_messages_kernel<false>, grid, block,
+                             (hipStream_t)stream, nullptr, (const uint32_t *)dev_state, (uint64_t)count, (uint32_t)rm.xorout,
+                             (uint8_t *)dev_msgs, dev_msg_offsets, (uint32_t)hash_off, status, mism);
     return e == hipSuccess ? MCHECKSUM_GPU_OK : hip_err(e, seal ? "state seal" : "state verify");
 }
 
@@ -1068,6 +1103,41 @@ int mchecksum_gpu_seal_detached_messages(const char *hash_method, void *dev_msgs
     return offsets_call(c);
 }
 
+// The detached calls with both sides by address list: the payloads' addresses ride where their table does and the
+// eager messages' where theirs does, with no buffer under either (offsets_call.h: OffsetsCall::both_lists).
+int mchecksum_gpu_verify_detached_message_list(const char *hash_method, const uint64_t *dev_msg_addr,
+                                               const uint64_t *dev_msg_len, size_t hash_offset,
+                                               const uint64_t *dev_payload_addr, const uint64_t *dev_payload_len,
+                                               size_t count, uint8_t *dev_status, uint32_t *dev_mismatches, void *stream) {
+    OffsetsCall c{kOpVerify, hash_method, nullptr, dev_payload_addr, count};
+    c.frame = kFrameDetached;
+    c.both_lists = true;
+    c.payload_len = dev_payload_len;
+    c.hdr_off = dev_msg_addr;
+    c.msg_len = dev_msg_len;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.mismatches = dev_mismatches;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
+int mchecksum_gpu_seal_detached_message_list(const char *hash_method, const uint64_t *dev_msg_addr,
+                                             const uint64_t *dev_msg_len, size_t hash_offset,
+                                             const uint64_t *dev_payload_addr, const uint64_t *dev_payload_len, size_t count,
+                                             uint8_t *dev_status, void *stream) {
+    OffsetsCall c{kOpSeal, hash_method, nullptr, dev_payload_addr, count};  // (the slots are written through their addresses)
+    c.frame = kFrameDetached;
+    c.both_lists = true;
+    c.payload_len = dev_payload_len;
+    c.hdr_off = dev_msg_addr;
+    c.msg_len = dev_msg_len;
+    c.hash_off = hash_offset;
+    c.status = dev_status;
+    c.stream = stream;
+    return offsets_call(c);
+}
+
 int mchecksum_gpu_verify_rpc_messages(const char *header_method, const char *payload_method, int kind, const void *dev_buf,
                                       const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
                                       size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
@@ -1223,6 +1293,20 @@ int mchecksum_gpu_state_seal_messages(const char *hash_method, const void *dev_s
                                       void *stream) {
     return state_messages_call(true, hash_method, dev_state, count, dev_msgs, dev_msg_offsets, hash_offset, dev_status,
                                nullptr, stream);
+}
+
+int mchecksum_gpu_state_verify_message_list(const char *hash_method, const void *dev_state, size_t count,
+                                            const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t hash_offset,
+                                            uint8_t *dev_status, uint32_t *dev_mismatches, void *stream) {
+    return state_messages_call(false, hash_method, dev_state, count, nullptr, dev_msg_addr, hash_offset, dev_status,
+                               dev_mismatches, stream, true, dev_msg_len);
+}
+
+int mchecksum_gpu_state_seal_message_list(const char *hash_method, const void *dev_state, size_t count,
+                                          const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t hash_offset,
+                                          uint8_t *dev_status, void *stream) {
+    return state_messages_call(true, hash_method, dev_state, count, nullptr, dev_msg_addr, hash_offset, dev_status, nullptr,
+                               stream, true, dev_msg_len);
 }
 
 int mchecksum_gpu_state_init(const char *hash_method, void *dev_state, size_t count, void *stream) {

@@ -43,6 +43,10 @@ struct OffsetsCall {
     // and msg_len their lengths; that side's buffer pointer (src, a pack's dst, a seal's out) is null
     bool list = false;
     const uint64_t *msg_len = nullptr;
+    // kFrameDetached with both sides by address list: src_off holds the payloads' addresses and payload_len their
+    // lengths, hdr_off the eager messages' addresses and msg_len theirs; src and hdr are null
+    bool both_lists = false;
+    const uint64_t *payload_len = nullptr;
 };
 
 constexpr bool op_copies(BatchOp op) { return op == kOpPack || op == kOpUnpack; }
@@ -55,19 +59,22 @@ constexpr bool op_copies(BatchOp op) { return op == kOpPack || op == kOpUnpack; 
 struct OffsetsNeeds {
     bool out, dst, hdr, expected, method_first;
     bool msg_len = false, src_buf = true, dst_buf = true;
+    bool payload_len = false, hdr_buf = true;  // both sides by list: a second lengths array, and no buffer under either
 };
-constexpr OffsetsNeeds offsets_needs(BatchOp op, MsgFrame frame, bool list = false) {
+constexpr OffsetsNeeds offsets_needs(BatchOp op, MsgFrame frame, bool list = false, bool both_lists = false) {
     return {op == kOpChecksum || op == kOpUpdate || (op == kOpSeal && frame != kFrameDetached && !list),  // values or hashes stored
             op_copies(op), frame == kFrameDetached, op == kOpVerify && frame == kFramePayloads,
             op_copies(op) || op == kOpSeal || frame == kFrameDetached || frame == kFrameRpc,
-            list, !list || op == kOpPack, !list || op != kOpPack};
+            list || both_lists, !(list || both_lists) || op == kOpPack, !list || op != kOpPack,
+            both_lists, !both_lists};
 }
 // Whether a call lacks a pointer it must supply: an empty batch needs no buffers (not even the one-entry table).
 inline bool offsets_lacks_pointer(const OffsetsCall &c) {
-    const OffsetsNeeds need = offsets_needs(c.op, c.frame, c.list);
+    const OffsetsNeeds need = offsets_needs(c.op, c.frame, c.list, c.both_lists);
     return c.count && ((need.src_buf && !c.src) || !c.src_off || (need.out && !c.out) ||
-                       (need.dst && ((need.dst_buf && !c.dst) || !c.dst_off)) || (need.hdr && (!c.hdr || !c.hdr_off)) ||
-                       (need.expected && !c.expected) || (need.msg_len && !c.msg_len));
+                       (need.dst && ((need.dst_buf && !c.dst) || !c.dst_off)) ||
+                       (need.hdr && ((need.hdr_buf && !c.hdr) || !c.hdr_off)) || (need.expected && !c.expected) ||
+                       (need.msg_len && !c.msg_len) || (need.payload_len && !c.payload_len));
 }
 
 // The kernels' argument of a call: pack = the model's table pack, shift = its
@@ -99,6 +106,13 @@ inline BatchArgs batch_args_of(const OffsetsCall &c, const void *pack, const voi
         if (c.op == kOpPack) a.copy_dst = nullptr;
         else a.base = nullptr;
         if (c.op == kOpSeal) a.msgs = nullptr;
+    }
+    if (c.both_lists) {
+        // both tables' entries are whole addresses: null buffers whatever the call holds, and a length array each
+        a.set_rpc_list_len(c.payload_len);
+        a.set_slot_list_len(c.msg_len);
+        a.base = nullptr;
+        a.msgs = nullptr;
     }
     a.status = c.status;
     a.mismatches = c.mismatches;

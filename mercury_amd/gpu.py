@@ -1068,6 +1068,138 @@ def pack_rpc_message_list(src: torch.Tensor, src_offsets: torch.Tensor, msg_addr
     return status
 
 
+# the (addr, len) pair of either side of the *_detached_message_list calls: rpc_message_list under the name it has there
+address_list = rpc_message_list
+
+
+def _check_addr_list(addr, lens, addr_host, len_host, names, count=None):
+    """One address list of a detached list call, and its host copies if given
+    (the two go together); returns (count, host addresses, host lengths)."""
+    _check_i64_table(addr, names[0], count)
+    if count is None:
+        count = addr.numel()
+    _check_i64_table(lens, names[1], count)
+    if addr.numel() != count or lens.numel() != count:
+        raise GpuChecksumError(f"{names[0]} and {names[1]} need the same number of entries as the other arrays")
+    if (addr_host is None) != (len_host is None):
+        raise GpuChecksumError(f"the host copies of {names[0]} and {names[1]} go together")
+    if addr_host is None:
+        return count, None, None
+    import numpy as np
+    ah, lh = np.asarray(addr_host, dtype=np.uint64), np.asarray(len_host, dtype=np.uint64)
+    if len(ah) != count or len(lh) != count:
+        raise GpuChecksumError(f"the host copies do not match {names[0]} / {names[1]}")
+    return count, ah, lh
+
+
+def _check_msg_list(msg_addr, msg_len, addr_host, len_host, hash_offset: int, written: bool, count=None) -> int:
+    """The eager messages of a detached list call; returns count.  With both
+    host arrays, the slots that a seal writes must not overlap one another."""
+    if hash_offset < 0 or hash_offset > 1 << 30:
+        raise GpuChecksumError("hash_offset must lie in 0..2^30")
+    count, ah, lh = _check_addr_list(msg_addr, msg_len, addr_host, len_host, ("msg_addr", "msg_len"), count)
+    if written and ah is not None and count > 1:
+        import numpy as np
+        with np.errstate(over="ignore"):
+            slots = np.sort(ah[(ah + lh >= ah) & (lh >= np.uint64(hash_offset + 4))])  # (each + hash_offset: the same order)
+        if np.any(slots[1:] - slots[:-1] < np.uint64(4)):
+            raise GpuChecksumError("hash slots that are written overlap one another")
+    return count
+
+
+def verify_detached_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, payload_addr: torch.Tensor,
+                                 payload_len: torch.Tensor, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                                 addr_host=None, len_host=None, payload_addr_host=None, payload_len_host=None,
+                                 status=None, mismatches=None):
+    """verify_detached_messages with both sides addressed by lists
+    (mchecksum_gpu_verify_detached_message_list): eager message i is the
+    msg_len[i] bytes at the device address msg_addr[i], payload i the
+    payload_len[i] bytes at payload_addr[i] -- four device int64 tensors of
+    `count` entries (rpc_message_list builds either pair), every payload and
+    every message wherever it lies.  Verdicts are verify_detached_messages';
+    returns (status, mismatch count).  A message without its slot and an empty
+    payload are never dereferenced (their addresses may be 0); a payload whose
+    end wraps the address space fails its entry."""
+    count = _check_msg_list(msg_addr, msg_len, addr_host, len_host, hash_offset, False)
+    _check_addr_list(payload_addr, payload_len, payload_addr_host, payload_len_host, ("payload_addr", "payload_len"), count)
+    status, mism = _verdict_buffers(count, msg_addr.device, status, mismatches)
+    _same_device(msg_addr, msg_len=msg_len, payload_addr=payload_addr, payload_len=payload_len,
+                 status=None if status is False else status, mismatches=None if mism is False else mism)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_verify_detached_message_list(method.encode(), msg_addr.data_ptr(), msg_len.data_ptr(),
+                                                               hash_offset, payload_addr.data_ptr(),
+                                                               payload_len.data_ptr(), count, _ptr(status), _ptr(mism),
+                                                               _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_detached_message_list")
+    return status, mism
+
+
+def seal_detached_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, payload_addr: torch.Tensor,
+                               payload_len: torch.Tensor, hash_offset: int = 16, method: str = "crc32c", stream=None,
+                               addr_host=None, len_host=None, payload_addr_host=None, payload_len_host=None,
+                               status=None):
+    """Sender side of verify_detached_message_list
+    (mchecksum_gpu_seal_detached_message_list): the CRC of payload i is stored
+    network-order in the 4 bytes at msg_addr[i] + hash_offset, through the
+    address; no other byte is written.  The slots must not overlap one another;
+    with both host arrays of the messages given that is checked here.  Returns
+    status as seal_detached_messages does."""
+    count = _check_msg_list(msg_addr, msg_len, addr_host, len_host, hash_offset, True)
+    _check_addr_list(payload_addr, payload_len, payload_addr_host, payload_len_host, ("payload_addr", "payload_len"), count)
+    status = _seal_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, payload_addr=payload_addr, payload_len=payload_len,
+                 status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_seal_detached_message_list(method.encode(), msg_addr.data_ptr(), msg_len.data_ptr(),
+                                                             hash_offset, payload_addr.data_ptr(), payload_len.data_ptr(),
+                                                             count, _ptr(status), _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_detached_message_list")
+    return status
+
+
+def state_verify_message_list(state: torch.Tensor, msg_addr: torch.Tensor, msg_len: torch.Tensor, hash_offset: int = 16,
+                              method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None,
+                              mismatches=None):
+    """state_verify_messages with the eager messages addressed by a list
+    (mchecksum_gpu_state_verify_message_list): the end of a pull hashed in
+    stages whose update_segments calls took the payloads by address.  Returns
+    (status, mismatch count) as verify_detached_message_list."""
+    count = _check_msg_list(msg_addr, msg_len, addr_host, len_host, hash_offset, False)
+    _check_state(state, method, count, "state")
+    status, mism = _verdict_buffers(count, msg_addr.device, status, mismatches)
+    _same_device(msg_addr, msg_len=msg_len, state=state, status=None if status is False else status,
+                 mismatches=None if mism is False else mism)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_state_verify_message_list(method.encode(), state.data_ptr(), count,
+                                                            msg_addr.data_ptr(), msg_len.data_ptr(), hash_offset,
+                                                            _ptr(status), _ptr(mism),
+                                                            _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_verify_message_list")
+    return status, mism
+
+
+def state_seal_message_list(state: torch.Tensor, msg_addr: torch.Tensor, msg_len: torch.Tensor, hash_offset: int = 16,
+                            method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None):
+    """The sender's mirror of state_verify_message_list
+    (mchecksum_gpu_state_seal_message_list): the CRC each state has reached,
+    stored network-order in its message's slot through the address.  Returns
+    status as seal_detached_message_list."""
+    count = _check_msg_list(msg_addr, msg_len, addr_host, len_host, hash_offset, True)
+    _check_state(state, method, count, "state")
+    status = _seal_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, state=state, status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_state_seal_message_list(method.encode(), state.data_ptr(), count, msg_addr.data_ptr(),
+                                                          msg_len.data_ptr(), hash_offset, _ptr(status),
+                                                          _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_state_seal_message_list")
+    return status
+
+
 def _torch_owned(stream, handle: int, device) -> bool:
     """Whether `handle` (the hipStream_t a call ran on, given `stream` as passed)
     is a stream torch created and never destroys: a torch.cuda.Stream from its

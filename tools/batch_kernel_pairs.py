@@ -26,7 +26,9 @@ launch_plan.h), or <LOG2G, MODE, OP, NT, LIGHT, DETACHED[, RPC]> (two bools),
 or <LOG2G, MODE, OP, NT, LIGHT, FRAME> (MsgFrame, launch_plan.h: the enum's
 type is part of the demangled name, "(mck::MsgFrame)3", which tells it from the
 bool spelling), or <LOG2G, MODE, OP, NT, LIGHT, FRAME, LIST> (a bool behind the
-MsgFrame: the message side by address list, "verify_rpc_list").  In these a detached kernel's operation reads
+MsgFrame: the message side by address list, "verify_rpc_list"), or <..., FRAME,
+LIST, BOTH> (a second bool: both sides of a detached call by address list,
+"verify_detached_both").  In these a detached kernel's operation reads
 "verify_detached" / "seal_detached" and a whole-RPC kernel's "verify_rpc" /
 "seal_rpc" / "pack_rpc" / "unpack_rpc", so both spellings pair by what a kernel
 is.  Exit status 1 unless the pairing is one to one and every pair is equal in
@@ -55,13 +57,15 @@ def key_of(name):
     a = [{"true": 1, "false": 0}.get(t, t) for t in raw]
     a = [int(re.sub(r"^\(.*\)", "", t)) if isinstance(t, str) else t for t in a]
     lg, mode = a[0], a[1]
-    if len(a) == 5 or (len(a) in (6, 7) and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED[, RPC] or FRAME]>
+    if len(a) == 5 or (len(a) in (6, 7, 8) and width == 32):  # <LOG2G, MODE, OP, NT, LIGHT or SPLIT[, DETACHED[, RPC] or FRAME]>
         op, nt, last = a[2], a[3], a[4]
         light, split = (last, 0) if width == 32 else (0, last)
         if len(a) >= 6 and "MsgFrame" in raw[5]:  # MsgFrame: payloads (in place is a run-time field), -, detached, RPC
             frame = ["", None, "_detached", "_rpc"][a[5]]
-            if len(a) == 7 and a[6]:  # LIST: the message side by address list
+            if len(a) >= 7 and a[6]:  # LIST: the message side by address list
                 frame += "_list"
+            if len(a) == 8 and a[7]:  # BOTH: the payloads and the slots of a detached call by address list
+                frame += "_both"
             return (width, lg, MODES[mode], OPS[op] + frame, nt, light, split)
         if len(a) >= 6 and a[5]:  # DETACHED: the slot of a verify or a seal in another buffer
             return (width, lg, MODES[mode], OPS[op] + "_detached", nt, light, split)
