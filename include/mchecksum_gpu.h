@@ -1298,6 +1298,124 @@ mchecksum_gpu_pack_xdr_messages(const char *hash_method,
     const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
     size_t hash_offset, uint8_t *dev_status, void *stream);
 
+/* Whole RPC messages of an XDR build: the core header, its flags and the
+ * fields in one pass -- what mchecksum_gpu_verify_rpc_messages and its three
+ * siblings are for the default build.  The core header is not XDR-encoded
+ * (hg_core_header_request_proc / _response_proc are the same in both builds),
+ * so an XDR receiver that drains a multi-recv buffer stood where the default
+ * build did: a launch of verify_core_headers and one of verify_xdr_messages,
+ * two status arrays to join on the host, a payload vouched for under a corrupt
+ * header, and every message flagged MORE_DATA reported corrupt because the
+ * schema was walked over its bulk descriptor (Mercury's XDR sender refuses to
+ * make such messages, src/mercury.c:718-721; a receiver must not trust a peer
+ * on that).  These four calls run the XDR walk inside the RPC frame.
+ *
+ * By reference, not restated:
+ *   - Message i, L, `kind`, `more` (bit 0 of the flags byte as it sits in the
+ *     buffer), the other range and R, the backwards-table rule, hash_offset >=
+ *     16, hash_offset + 4 <= payload_offset and the 2^30 cap on hash_offset:
+ *     the plain RPC calls' (mchecksum_gpu_verify_rpc_messages ..
+ *     mchecksum_gpu_pack_rpc_messages).
+ *   - fields / nfields, the 64-entry cap, MCHECKSUM_XDR_SINT, "bytes after the
+ *     schema's end are ignored" on the receiver and "the schema consumes the
+ *     image exactly, the message has no slack" on the sender, the image's
+ *     layout, the read padding and the no-overlap rule: the XDR message calls'
+ *     (mchecksum_gpu_verify_xdr_messages .. mchecksum_gpu_pack_xdr_messages).
+ *   - header_method: a 16-bit model of either bit order; payload_method: a
+ *     reflected 32-bit model.
+ *   - Argument checks, in this order: MCHECKSUM_GPU_EINVAL (a NULL required
+ *     pointer with count > 0, an unknown kind, the offsets rules, a bad
+ *     schema, count > 2^31), then both methods' _EMETHOD ahead of the device,
+ *     then _ENODEV.  count == 0 needs no buffers but passes the same checks.
+ *   - Statuses: MCHECKSUM_GPU_RPC_* and, for the copying two,
+ *     MCHECKSUM_GPU_COPY_RPC_MISFIT; dev_counts: MCHECKSUM_GPU_RPC_CLASSES
+ *     words for verify, MCHECKSUM_GPU_COPY_RPC_CLASSES for unpack, zeroed by
+ *     the caller; dev_status and dev_counts may each be NULL.
+ *   - Layout, work-queue slot and loads as the XDR message calls pick them for
+ *     the same count; asynchronous and stream-ordered; no workspace; capture-
+ *     safe after mchecksum_gpu_prepare() of BOTH methods (a replay reads the
+ *     current contents).  Fail closed: a call whose throughput layout gave up
+ *     a wait adds 1 to the error word, a verify or unpack adds `count` to
+ *     dev_counts[MCHECKSUM_GPU_RPC_FAULT], and every status becomes
+ *     MCHECKSUM_GPU_RPC_FAULT (flagged by a short launch after the walk, made
+ *     only by calls that hold a work-queue slot and pass dev_status); bytes
+ *     written for messages it cannot vouch for are unspecified.
+ *
+ * First rule that matches.
+ * verify:
+ *   1. L < 16                                    -> SHORT (no byte is read)
+ *   2. the core header's CRC-16 differs          -> HEADER
+ *   3. `more`                                    -> DEFERRED: no byte behind
+ *                                                   the core header is read
+ *   4. L < payload_offset                        -> SHORT
+ *   5. the schema runs past the message          -> SHORT (shorter than its own
+ *                                                   fields need)
+ *   6. the value checksum_xdr would return differs from the network-order u32
+ *      at hash_offset                            -> PAYLOAD
+ *   7. OK
+ * unpack: rules 1-5, then decoded length != R -> MISFIT, then PAYLOAD, then
+ *   OK.  What is written does not wait for the verdicts: message i's
+ *   destination range is written iff L >= 16, `more` is clear, L >=
+ *   payload_offset, the schema fits and the decoded length == R; it then holds
+ *   the decoded bytes AS RECEIVED, whatever rules 2 and 6 say.  Nothing of a
+ *   SHORT, DEFERRED or MISFIT message's range is written.
+ * seal:
+ *   1. L < 16                                    -> SHORT, nothing written
+ *   2. `more`                                    -> DEFERRED, the header's
+ *                                                   CRC-16 alone (2 bytes)
+ *   3. L < payload_offset, or the schema runs past the message
+ *                                                -> SHORT, nothing written
+ *   4. OK: the value big-endian at hash_offset and the CRC-16 at 12 (request)
+ *      or 4 (response): exactly those 6 bytes.
+ * pack:
+ *   1. L < 16                                    -> SHORT
+ *   2. `more`                                    -> DEFERRED: the CRC-16 alone,
+ *                                                   the source range is not read
+ *   3. L < payload_offset                        -> SHORT
+ *   4. the schema does not consume the image exactly, or L != payload_offset +
+ *      the encoded length                        -> MISFIT, nothing written
+ *   5. OK: exactly the XDR bytes (pads included), the 4 hash bytes and the 2
+ *      CRC-16 bytes.
+ *
+ * Not offered: the address-list (_list) forms of these calls, and 64-bit
+ * payload methods (the HG slot is 32 bits).
+ * Cost (MI355X), each call against the two launches it
+ * replaces (the core-header call and the XDR message call), iovec schema:
+ * 0.97 .. 1.00x at 8192 x 64 KiB and 0.81 .. 0.90x at 64 x 4 KiB, but SLOWER
+ * at 65536 x 4 KiB -- verify 1.05x, seal 1.07x, unpack 1.03x, pack 1.09x,
+ * beyond the measurement's spread: there the header read ahead of each
+ * message's walk is not hidden.  A caller of that shape that needs neither the
+ * DEFERRED class nor one status array may keep the two launches. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_rpc_xdr_messages(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_buf, const uint64_t *dev_msg_offsets,
+    size_t count, size_t payload_offset, size_t hash_offset,
+    uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_rpc_xdr_messages(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, void *dev_buf, const uint64_t *dev_msg_offsets,
+    size_t count, size_t payload_offset, size_t hash_offset,
+    uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_rpc_xdr_messages(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_buf, const uint64_t *dev_msg_offsets,
+    size_t count, size_t payload_offset, size_t hash_offset, void *dev_dst,
+    const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_counts,
+    void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_rpc_xdr_messages(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_src, const uint64_t *dev_src_offsets,
+    void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+    size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+    void *stream);
+
 /* The data-dependent lengths the XDR message tables are built from, computed
  * where the data is: one small launch per call that reads the integer fields
  * only, with the walks' own bounds tests.

@@ -43,7 +43,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_seal_rpc_message_list", "mchecksum_gpu_unpack_rpc_message_list",
                "mchecksum_gpu_pack_rpc_message_list", "mchecksum_gpu_verify_detached_message_list",
                "mchecksum_gpu_seal_detached_message_list", "mchecksum_gpu_state_verify_message_list",
-               "mchecksum_gpu_state_seal_message_list")
+               "mchecksum_gpu_state_seal_message_list", "mchecksum_gpu_verify_rpc_xdr_messages",
+               "mchecksum_gpu_seal_rpc_xdr_messages", "mchecksum_gpu_unpack_rpc_xdr_messages",
+               "mchecksum_gpu_pack_rpc_xdr_messages")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -157,6 +159,18 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_pack_xdr_messages.argtypes = [c_char_p, ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p]
     L.mchecksum_gpu_pack_xdr_messages.restype = c_int
+    # whole RPC messages of an XDR build: (header_method, payload_method, kind, fields, nfields, ...) then the XDR
+    # message call's arguments from dev_buf on (pack: from dev_src on); verify and unpack end (status, counts, stream)
+    rpc_xdr = [c_char_p, c_char_p, c_int, ctypes.POINTER(XdrField), c_size_t]
+    L.mchecksum_gpu_verify_rpc_xdr_messages.argtypes = rpc_xdr + xdr_msg[3:] + [c_void_p, c_void_p, c_void_p]
+    L.mchecksum_gpu_verify_rpc_xdr_messages.restype = c_int
+    L.mchecksum_gpu_seal_rpc_xdr_messages.argtypes = rpc_xdr + xdr_msg[3:] + [c_void_p, c_void_p]
+    L.mchecksum_gpu_seal_rpc_xdr_messages.restype = c_int
+    L.mchecksum_gpu_unpack_rpc_xdr_messages.argtypes = rpc_xdr + xdr_msg[3:] + [c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                               c_void_p]
+    L.mchecksum_gpu_unpack_rpc_xdr_messages.restype = c_int
+    L.mchecksum_gpu_pack_rpc_xdr_messages.argtypes = rpc_xdr + L.mchecksum_gpu_pack_xdr_messages.argtypes[3:]
+    L.mchecksum_gpu_pack_rpc_xdr_messages.restype = c_int
     # (fields, nfields, src, src_offsets, count, sizes, status, stream)
     L.mchecksum_gpu_xdr_encoded_sizes.argtypes = [ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p, c_size_t,
                                                   c_void_p, c_void_p, c_void_p]

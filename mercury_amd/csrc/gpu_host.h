@@ -139,6 +139,10 @@ int get_pack(DevCtx *c, int idx, int log2g, const void **pack);
 // Z^n shift pack of a 32/64-bit model, the byte table of a 16-bit one
 // (g_mu on creation only).
 int get_ext(DevCtx *c, int idx, const void **out);
+// The header pack of 16-bit model idx and core header kind (launch_plan.h,
+// RpcHdrPack; mchecksum_gpu.hip), for the plain RPC calls and the XDR walks in
+// the RPC frame alike (g_mu on creation only).
+int get_rpc_pack(DevCtx *c, int idx, int kind, const void **out);
 // Work-queue slot bank for one launch of a throughput (non-light) batch
 // kernel on `stream`, exclusive to that launch until it completes; empty
 // (static split) for a launch being captured into a graph or when no slot is

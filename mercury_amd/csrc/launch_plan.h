@@ -447,6 +447,61 @@ MCK_HOST_DEVICE_INLINE uint32_t rpc_pack_class(uint64_t L, bool more, uint64_t p
     return L - pay_off != R ? kRpcMisfit : kRpcOk;
 }
 
+// ---- whole RPC messages in XDR mode: mchecksum_gpu_verify_rpc_xdr_messages,
+// ---- _seal_rpc_xdr_messages, _unpack_rpc_xdr_messages, _pack_rpc_xdr_messages ----
+//
+// The frame above around the XDR walkers (mchecksum_gpu_ext.hip: xdr_message,
+// xdr_pack_message): what lies behind pay_off is not hashed as bytes but walked
+// by a field schema, so two facts of the walk enter the rules.  `fits`: the
+// schema stays inside [pay_off, L) (xdr_decoded_len; the sender's `exact`: the
+// schema consumes the image exactly, xdr_encoded_len).  `decoded` / `encoded`:
+// the length the pre-walk found for the other side.  Both are of a message the
+// walk may touch only (rpc_hashes_payload): every rule that reads them stands
+// behind the three that say so, and no byte behind the core header is read for
+// a message those three decide.  The kernels' rules and the CPU's
+// (tests/native/rpc_xdr_msg.cpp): the same code.
+//
+// Whether the schema is walked over the message: verify and seal.
+MCK_HOST_DEVICE_INLINE bool rpc_xdr_walks(uint64_t L, bool more, uint64_t pay_off) { return rpc_hashes_payload(L, more, pay_off); }
+// The receiver's verdict, first matching rule first.  payload_ok: of a message whose schema fits only.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_xdr_verify_class(uint64_t L, bool hdr_ok, bool more, uint64_t pay_off, bool fits,
+                                                     bool payload_ok) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (!hdr_ok) return kRpcHeader;
+    if (more) return kRpcDeferred;
+    if (L < pay_off || !fits) return kRpcShort;  // shorter than its headers, or than its own fields need
+    return payload_ok ? kRpcOk : kRpcPayload;
+}
+// The sender's in place: kRpcOk = both hashes are written, kRpcDeferred = the header's alone, kRpcShort = nothing.
+MCK_HOST_DEVICE_INLINE uint32_t rpc_xdr_seal_class(uint64_t L, bool more, uint64_t pay_off, bool fits) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (more) return kRpcDeferred;
+    return L < pay_off || !fits ? kRpcShort : kRpcOk;
+}
+// unpack: whether the destination range (R bytes) is written, and the fields hashed.  The header's verdict does not enter.
+MCK_HOST_DEVICE_INLINE bool rpc_xdr_unpacks(uint64_t L, bool more, uint64_t pay_off, bool fits, uint64_t decoded, uint64_t R) {
+    return rpc_hashes_payload(L, more, pay_off) && fits && decoded == R;
+}
+MCK_HOST_DEVICE_INLINE uint32_t rpc_xdr_unpack_class(uint64_t L, bool hdr_ok, bool more, uint64_t pay_off, bool fits,
+                                                     uint64_t decoded, uint64_t R, bool payload_ok) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (!hdr_ok) return kRpcHeader;
+    if (more) return kRpcDeferred;
+    if (L < pay_off || !fits) return kRpcShort;
+    if (decoded != R) return kRpcMisfit;
+    return payload_ok ? kRpcOk : kRpcPayload;
+}
+// pack: whether the image is read and its XDR bytes written.  exact, encoded: of the image, the source range.
+MCK_HOST_DEVICE_INLINE bool rpc_xdr_packs(uint64_t L, bool more, uint64_t pay_off, bool exact, uint64_t encoded) {
+    return rpc_hashes_payload(L, more, pay_off) && exact && L - pay_off == encoded;
+}
+MCK_HOST_DEVICE_INLINE uint32_t rpc_xdr_pack_class(uint64_t L, bool more, uint64_t pay_off, bool exact, uint64_t encoded) {
+    if (L < kRpcHdrBytes) return kRpcShort;
+    if (more) return kRpcDeferred;
+    if (L < pay_off) return kRpcShort;
+    return !exact || L - pay_off != encoded ? kRpcMisfit : kRpcOk;
+}
+
 // One instantiation of the batch kernels (crc32c_batch_kernel,
 // crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
 struct KernelKey {

@@ -1207,19 +1207,86 @@ enum XdrOp : int {
     // and seals it (xdr_pack_message, a sibling walker with arguments and
     // kernels of its own: XdrPackArgs).
     kXdrPack,
+    // The four message operations in the RPC frame (launch_plan.h, "whole RPC
+    // messages in XDR mode"): mchecksum_gpu_verify_rpc_xdr_messages, _seal_,
+    // _unpack_, _pack_.  The same walks between a prologue -- sixteen lanes
+    // load the core header and look up its CRC-16 terms; the flags byte and
+    // the length decide for the whole wave whether the walk starts -- and an
+    // epilogue that gives the message its class (xdr_rpc_header, _hdr_crc).
+    // Kernels of their own (xdr_rpc_kernel, xdr_rpc_fast_kernel): the five
+    // operations above keep theirs, instantiated as they were.
+    kXdrRpcVerify,
+    kXdrRpcSeal,
+    kXdrRpcUnpack,
+    kXdrRpcPack,
 };
+constexpr bool xdr_op_rpc(int op) { return op >= kXdrRpcVerify; }
+// What the walk does between the frame's two ends: the operation without its frame.
+constexpr int xdr_op_walk(int op) { return xdr_op_rpc(op) ? op - kXdrRpcVerify + kXdrVerify : op; }
+static_assert(xdr_op_walk(kXdrRpcVerify) == kXdrVerify && xdr_op_walk(kXdrRpcSeal) == kXdrSeal &&
+                  xdr_op_walk(kXdrRpcUnpack) == kXdrUnpack && xdr_op_walk(kXdrRpcPack) == kXdrPack,
+              "the RPC operations name the message operations in their order");
 
 // The message operations' arguments beside XdrArgs (whose `out` they leave unused).
 struct XdrMsg {
     uint64_t pay_off, hash_off;
     uint8_t *dst;             // unpack
     const uint64_t *dst_off;  // unpack: count + 1 entries
-    uint32_t *mism;           // verify, unpack
+    uint32_t *mism;           // verify, unpack (the RPC frame: the 6 or 7 class counts)
 };
 struct XdrMsgArgs {
     XdrArgs a;
     XdrMsg x;
 };
+
+// ---- the RPC frame around a walk ----
+// The header model's pack as a kernel reads it once, at entry (scalar loads).
+struct XdrRpcFront {
+    rpc_tab_t tab = nullptr;  // RpcHdrPack::row, in global memory: one 2-byte load per header byte and message
+    uint32_t kind = 0, c = 0;
+};
+__device__ __forceinline__ XdrRpcFront xdr_rpc_front(const void *hdr_pack) {
+    const mck::RpcHdrPack *hp = reinterpret_cast<const mck::RpcHdrPack *>(hdr_pack);
+    XdrRpcFront r;
+    r.tab = (rpc_tab_t)uniform64(reinterpret_cast<uint64_t>(&hp->row[0][0]));
+    r.kind = hp->kind;
+    r.c = hp->c;
+    return r;
+}
+// Prologue, the whole wave, ahead of every load behind the core header: lanes
+// 0..15 load a header byte each (none of a message without a whole header),
+// the flags byte is read from its lane, and each lane's term of the CRC-16 is
+// looked up -- that load is in flight under the walk and joined in the epilogue
+// (xdr_rpc_hdr_crc), as the plain RPC kernels do it (crc_gpu_crc32.h).
+struct XdrRpcHdr {
+    bool more = false;
+    uint32_t term = 0;
+};
+__device__ __forceinline__ XdrRpcHdr xdr_rpc_header(const XdrRpcFront &r, const uint8_t *msg, uint64_t L, uint32_t lane) {
+    const bool whole = L >= mck::kRpcHdrBytes;
+    uint32_t hb = 0;
+    XdrRpcHdr h;
+    if (whole && lane < mck::kRpcHdrBytes) hb = global_ptr(msg, true)[lane];
+    h.more = whole && (__builtin_amdgcn_readlane(hb, mck::rpc_flags_at(r.kind)) & 1u);
+    if (whole && lane < mck::kRpcHdrBytes) h.term = r.tab[mck::rpc_hdr_term_index(r.kind, lane, hb)];
+    return h;
+}
+// Epilogue, the whole wave: the image's terms XOR over the lanes that hold them; the wire hash is two identity terms.
+__device__ __forceinline__ void xdr_rpc_hdr_crc(const XdrRpcFront &r, uint32_t term, uint32_t lane, uint32_t *crc16,
+                                                uint32_t *wire) {
+    uint32_t t = lane < mck::rpc_img_bytes(r.kind) ? term : 0u;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) t ^= __shfl_xor(t, d, 64);
+    *crc16 = mck::rpc_hdr_crc(r.c, __builtin_amdgcn_readfirstlane(t));
+    const uint32_t hat = mck::rpc_hash_at(r.kind);
+    *wire = __builtin_amdgcn_readlane(term, hat) << 8 | __builtin_amdgcn_readlane(term, hat + 1);
+}
+// (byte stores: the two bytes share their granule with other header fields)
+__device__ __forceinline__ void xdr_rpc_store_crc16(uint8_t *msg, uint32_t kind, uint32_t crc16) {
+    const uint32_t hat = mck::rpc_hash_at(kind);
+    msg[hat] = (uint8_t)(crc16 >> 8);
+    msg[hat + 1] = (uint8_t)crc16;
+}
 
 // The length of the hashed stream of the message at [pos, end): the main
 // walk's steps and bounds tests, reading the INT fields only.  false: the
@@ -1264,29 +1331,54 @@ __device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, 
 // byte and combined into L.
 template <int W, int OP = kXdrChecksum, class Fast>
 __device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, uint64_t m, const xdr_reg_t<W> *tab,
-                                            uint32_t lane, Fast &&fast, uint32_t &nbad) {
+                                            uint32_t lane, Fast &&fast, uint32_t &nbad,
+                                            const XdrRpcFront &rf = XdrRpcFront{}) {
     using R = xdr_reg_t<W>;
-    enum : bool { MSG = OP != kXdrChecksum, VERIFY = OP == kXdrVerify || OP == kXdrUnpack, COPY = OP == kXdrUnpack };
+    enum : int { WALK = xdr_op_walk(OP) };
+    enum : bool {
+        RPC = xdr_op_rpc(OP),
+        MSG = WALK != kXdrChecksum,
+        VERIFY = WALK == kXdrVerify || WALK == kXdrUnpack,
+        COPY = WALK == kXdrUnpack
+    };
     static_assert(!MSG || W == 32, "the header's hash slot is 32 bits");
+    static_assert(WALK != kXdrPack, "the sender's walk is xdr_pack_message");
     uint64_t pos = a.off[m];
     const uint64_t end = a.off[m + 1];
     [[maybe_unused]] const uint64_t m0 = pos;
     R acc = (R)a.init;
     uint64_t last = 0;
     bool bad = end < pos;
-    if constexpr (MSG) {
+    // RPC: the frame's facts for the class.  `bad` is "the walk does not run"
+    // until the walk, and "it ran past the message" from then on.
+    [[maybe_unused]] uint64_t L = 0, decoded = 0, range = 0;
+    [[maybe_unused]] XdrRpcHdr h;
+    [[maybe_unused]] bool fits = false;
+    if constexpr (RPC) {
+        L = mck::rpc_len(pos, end);
+        h = xdr_rpc_header(rf, a.buf + pos, L, lane);
+        bad = !mck::rpc_xdr_walks(L, h.more, x.pay_off);  // SHORT or DEFERRED: no byte behind the core header is read
+        pos += x.pay_off;
+    } else if constexpr (MSG) {
         bad = bad || end - pos < x.pay_off;
         pos += x.pay_off;
     }
     // unpack: where the next decoded byte goes.  A message that does not fit
     // its slot is not walked at all: nothing of it is hashed or stored.
     [[maybe_unused]] uint8_t *d = nullptr;
-    if constexpr (COPY) {
+    if constexpr (COPY && RPC) {
+        const uint64_t d0 = x.dst_off[m];
+        range = mck::rpc_len(d0, x.dst_off[m + 1]);
+        fits = !bad && xdr_decoded_len(a, pos, end, &decoded);
+        bad = !mck::rpc_xdr_unpacks(L, h.more, x.pay_off, fits, decoded, range);
+        d = x.dst + d0;
+    } else if constexpr (COPY) {
         const uint64_t d0 = x.dst_off[m], d1 = x.dst_off[m + 1];
         uint64_t n = 0;
         bad = bad || d1 < d0 || !xdr_decoded_len(a, pos, end, &n) || n != d1 - d0;
         d = x.dst + d0;
     }
+    [[maybe_unused]] const bool walked = !bad;
     for (uint32_t f = 0; f < a.nf && !bad; f++) {
         const uint32_t kind = a.kind[f], sz = a.size[f];
         if (kind == MCHECKSUM_XDR_SKIP_IF_ZERO) {
@@ -1334,6 +1426,36 @@ __device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, u
         }
         if constexpr (COPY) d += len;
         pos += raw ? len : (len + 3) & ~3ull;
+    }
+    if constexpr (RPC) {
+        // The frame's epilogue: the class from launch_plan.h's ladders, the
+        // status byte, byte stores for the two hashes; a verifying workgroup
+        // counts its classes in LDS (rpc_wg_counts, added once per workgroup).
+        uint32_t crc16, wire;
+        xdr_rpc_hdr_crc(rf, h.term, lane, &crc16, &wire);
+        if (lane == 0) {
+            const uint32_t crc = (uint32_t)acc ^ (uint32_t)a.xorout;
+            uint32_t cls;
+            if constexpr (WALK == kXdrSeal) {
+                // (`bad`: the walk did not run, or ran past the message)
+                cls = mck::rpc_xdr_seal_class(L, h.more, x.pay_off, !bad);
+                uint8_t *msg = const_cast<uint8_t *>(a.buf) + m0;
+                if (cls == mck::kRpcOk) store_be32(msg + x.hash_off, crc);
+                if (cls != mck::kRpcShort) xdr_rpc_store_crc16(msg, rf.kind, crc16);
+            } else {
+                // (unpack: the bytes are stored as decoded; both verdicts are known only after them.  A pre-walk
+                // that fitted and a walk that then ran past -- the buffer changed under the call -- is SHORT.)
+                if constexpr (COPY) fits = fits && !(walked && bad);
+                else fits = !bad;
+                const bool pay_ok = !bad && load_be32(a.buf + m0 + x.hash_off) == crc;
+                if constexpr (COPY)
+                    cls = mck::rpc_xdr_unpack_class(L, crc16 == wire, h.more, x.pay_off, fits, decoded, range, pay_ok);
+                else cls = mck::rpc_xdr_verify_class(L, crc16 == wire, h.more, x.pay_off, fits, pay_ok);
+                atomicAdd(&rpc_wg_counts<COPY ? mck::kRpcCopyClasses : mck::kRpcClasses>()[cls], 1u);
+            }
+            if (a.status) a.status[m] = (uint8_t)cls;
+        }
+        return;
     }
     if (lane == 0) {
         const R crc = bad ? (R)0 : acc ^ (R)a.xorout;
@@ -1477,16 +1599,18 @@ __global__ __launch_bounds__(1024, 1) void xdr_msg_fast_kernel(XdrMsgArgs ma) {
 // (this launch holds the slot in its place, so the bank is still the call's):
 // if a wait of that launch gave up -- its fault flag is claimed -- every
 // status becomes 1.  The launch's own waves write verdicts until its end, so
-// only a launch after it can leave all of them flagged.
+// only a launch after it can leave all of them flagged.  value: what a flagged
+// status reads -- 1, or MCHECKSUM_GPU_RPC_FAULT from the calls in the RPC frame.
 struct XdrFlagArgs {
     const unsigned long long *queue;
     uint8_t *status;
     uint64_t count;
+    uint8_t value;
 };
 __global__ __launch_bounds__(256) void xdr_flag_kernel(XdrFlagArgs f) {
     if (!__hip_atomic_load(f.queue + kQFault * kQStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
     for (uint64_t m = (uint64_t)blockIdx.x * 256 + threadIdx.x; m < f.count; m += (uint64_t)gridDim.x * 256)
-        f.status[m] = 1;
+        f.status[m] = f.value;
 }
 
 // -------------------------------------------------------- XDR encoder ----
@@ -1556,16 +1680,35 @@ __device__ __forceinline__ bool xdr_encoded_len(const XdrArgs &a, const uint8_t 
 // One message (one wave, wave-uniform walk).  fast(s, len, &L, d) as in
 // xdr_message: it may hash the field of len bytes at s itself, continuing L,
 // and store it at d.
-template <class Fast>
+// OP: kXdrPack, or kXdrRpcPack -- the RPC frame around the same walk: the
+// message's own core header (the caller filled it but for the two hashes) is
+// read first, and an image is read only for a message that is eager and whole.
+template <int OP = kXdrPack, class Fast>
 __device__ __forceinline__ void xdr_pack_message(const XdrArgs &a, const XdrMsg &x, const XdrPack &p, uint64_t m,
-                                                 const uint32_t *tab, uint32_t lane, Fast &&fast) {
+                                                 const uint32_t *tab, uint32_t lane, Fast &&fast,
+                                                 const XdrRpcFront &rf = XdrRpcFront{}) {
+    static_assert(xdr_op_walk(OP) == kXdrPack, "the sender's walk");
+    enum : bool { RPC = xdr_op_rpc(OP) };
     const uint64_t m0 = a.off[m], end = a.off[m + 1];
     const uint64_t s0 = p.src_off[m], s1 = p.src_off[m + 1];
-    bool bad = end < m0 || s1 < s0 || end - m0 < x.pay_off;
     uint64_t n = 0;
-    bad = bad || !xdr_encoded_len(a, p.src + s0, s1 - s0, &n) || n != end - m0 - x.pay_off;
+    bool bad;
+    [[maybe_unused]] uint64_t L = 0;
+    [[maybe_unused]] XdrRpcHdr h;
+    [[maybe_unused]] bool exact = false;
+    if constexpr (RPC) {
+        L = mck::rpc_len(m0, end);
+        h = xdr_rpc_header(rf, a.buf + m0, L, lane);
+        // (a DEFERRED or SHORT message's source range is not read; a table that runs backwards is an empty image)
+        exact = mck::rpc_hashes_payload(L, h.more, x.pay_off) && xdr_encoded_len(a, p.src + s0, mck::rpc_len(s0, s1), &n);
+        bad = !mck::rpc_xdr_packs(L, h.more, x.pay_off, exact, n);
+    } else {
+        bad = end < m0 || s1 < s0 || end - m0 < x.pay_off;
+        bad = bad || !xdr_encoded_len(a, p.src + s0, s1 - s0, &n) || n != end - m0 - x.pay_off;
+    }
+    [[maybe_unused]] const bool packed = !bad;
     const uint8_t *s = p.src + s0;                                // the next image byte
-    const uint8_t *const s_end = p.src + s1;
+    const uint8_t *const s_end = p.src + (RPC ? s0 + mck::rpc_len(s0, s1) : s1);
     uint8_t *d = const_cast<uint8_t *>(a.buf) + m0 + x.pay_off;  // where the next XDR byte goes
     uint8_t *const d_end = const_cast<uint8_t *>(a.buf) + end;
     uint32_t acc = (uint32_t)a.init;
@@ -1621,6 +1764,20 @@ __device__ __forceinline__ void xdr_pack_message(const XdrArgs &a, const XdrMsg 
         s += len;
         d += wire;
     }
+    if constexpr (RPC) {
+        uint32_t crc16, wire_hash;
+        xdr_rpc_hdr_crc(rf, h.term, lane, &crc16, &wire_hash);
+        if (lane == 0) {
+            // (an image that changed under the call so that the walk ran past it: MISFIT, its bytes unspecified)
+            const uint32_t cls = mck::rpc_xdr_pack_class(L, h.more, x.pay_off, exact && !(packed && bad), n);
+            uint8_t *msg = const_cast<uint8_t *>(a.buf) + m0;
+            // (the XDR bytes are in place by now: they, the 4 hash bytes and the 2 CRC-16 bytes, no others)
+            if (cls == mck::kRpcOk) store_be32(msg + x.hash_off, acc ^ (uint32_t)a.xorout);
+            if (cls == mck::kRpcOk || cls == mck::kRpcDeferred) xdr_rpc_store_crc16(msg, rf.kind, crc16);
+            if (a.status) a.status[m] = (uint8_t)cls;
+        }
+        return;
+    }
     if (lane == 0) {
         // (the slot lies in the message's headers, outside every XDR byte)
         if (!bad) store_be32(const_cast<uint8_t *>(a.buf) + m0 + x.hash_off, acc ^ (uint32_t)a.xorout);
@@ -1668,6 +1825,98 @@ __global__ __launch_bounds__(1024, 1) void xdr_pack_fast_kernel(XdrPackArgs pa) 
     const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
                                              [&](uint64_t m) { xdr_pack_message(a, pa.x, pa.p, m, tab, lane, fast); });
     if (faulted && lane == 0 && a.err_word) atomicAdd(a.err_word, 1u);
+}
+
+// ------------------------------------------- XDR walks in the RPC frame ----
+//
+// mchecksum_gpu_verify_rpc_xdr_messages, _seal_, _unpack_, _pack_: the kernels
+// above with the frame's prologue and epilogue around each message's walk
+// (xdr_message / xdr_pack_message with an RPC operation), one latency and one
+// throughput kernel for the four operations.  Beside their twins' LDS they
+// hold the verifying calls' 6 or 7 class counts (rpc_wg_counts, 24 or 28
+// bytes); the header pack stays in global memory, as in the plain RPC kernels:
+// 6.5 KiB of rows for sixteen 2-byte loads a message do not earn a fill per
+// workgroup, and those loads are in flight under the walk.
+struct XdrRpcArgs : XdrMsgArgs {
+    const void *hdr_pack;  // launch_plan.h, RpcHdrPack: the header model's, of the call's kind
+};
+struct XdrRpcPackArgs : XdrPackArgs {
+    const void *hdr_pack;
+};
+template <int OP>
+using xdr_rpc_args_t = typename std::conditional<OP == kXdrRpcPack, XdrRpcPackArgs, XdrRpcArgs>::type;
+template <int OP>
+constexpr bool kXdrRpcCounts = OP == kXdrRpcVerify || OP == kXdrRpcUnpack;
+template <int OP>
+constexpr uint32_t kXdrRpcClasses = OP == kXdrRpcUnpack ? mck::kRpcCopyClasses : mck::kRpcClasses;
+
+template <int OP, class Fast>
+__device__ __forceinline__ void xdr_rpc_one(const xdr_rpc_args_t<OP> &ra, const XdrRpcFront &rf, uint64_t m,
+                                            const uint32_t *tab, uint32_t lane, Fast &&fast) {
+    if constexpr (OP == kXdrRpcPack) {
+        xdr_pack_message<OP>(ra.a, ra.x, ra.p, m, tab, lane, fast, rf);
+    } else {
+        uint32_t nbad = 0;  // (the plain frame's count: the classes are counted in LDS)
+        xdr_message<32, OP>(ra.a, ra.x, m, tab, lane, fast, nbad, rf);
+    }
+}
+
+// Latency layout: xdr_msg_kernel's workgroups.
+template <int OP>
+__global__ __launch_bounds__(256) void xdr_rpc_kernel(xdr_rpc_args_t<OP> ra) {
+    static_assert(xdr_op_rpc(OP), "the RPC frame's operations");
+    const XdrArgs &a = ra.a;
+    __shared__ uint32_t tab[256];
+    tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    const XdrRpcFront rf = xdr_rpc_front(ra.hdr_pack);
+    if (kXdrRpcCounts<OP> && threadIdx.x < kXdrRpcClasses<OP>) rpc_wg_counts<kXdrRpcClasses<OP>>()[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t m = uniform((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6))); m < a.count; m += nw)
+        xdr_rpc_one<OP>(ra, rf, m, tab, lane, [](const uint8_t *, uint64_t, uint32_t *, uint8_t *) { return false; });
+    if constexpr (kXdrRpcCounts<OP>) rpc_add_counts<kXdrRpcClasses<OP>>(ra.x.mism);  // once per workgroup and class
+}
+
+// Throughput layout: xdr_msg_fast_kernel's / xdr_pack_fast_kernel's workgroups,
+// tables and work queue.  Fail closed: the error word, a verifying call's
+// FAULT count, and the statuses after the launch (xdr_flag_kernel with
+// MCHECKSUM_GPU_RPC_FAULT).  The copying step loop: a table type of these
+// kernels' own, as above.
+struct XdrRpcTab32 : Tab32<false> {};
+template <int OP, bool NT>
+__global__ __launch_bounds__(1024, 1) void xdr_rpc_fast_kernel(xdr_rpc_args_t<OP> ra) {
+    static_assert(xdr_op_rpc(OP), "the RPC frame's operations");
+    const XdrArgs &a = ra.a;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kXdrMainLds<32> + 256 * sizeof(uint32_t)];
+    __shared__ WgQueue wgq;
+    uint32_t *tab = reinterpret_cast<uint32_t *>(lds + kXdrMainLds<32>);
+    if (threadIdx.x == 0) wg_queue_init(&wgq, a.queue, a.count);
+    const crc32_gpu_pack_t *pk = reinterpret_cast<const crc32_gpu_pack_t *>(a.pack);
+    const XdrRpcFront rf = xdr_rpc_front(ra.hdr_pack);
+    fill_lds32<false, 1024>(lds, pk);
+    if (threadIdx.x < 256) tab[threadIdx.x] = xdr_tab_entry<32>(a.rpoly, threadIdx.x);
+    if (kXdrRpcCounts<OP> && threadIdx.x < kXdrRpcClasses<OP>) rpc_wg_counts<kXdrRpcClasses<OP>>()[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 16u + (threadIdx.x >> 6));
+    const uint32_t nw = gridDim.x * 16u;
+    const uint32_t lc0 = (lane & 31u) << 2, lc1 = lc0 | 0x10000u;
+    auto fast = [&](const uint8_t *p, uint64_t len, uint32_t *reg, [[maybe_unused]] uint8_t *d) -> bool {
+        if (len < kXdrFastMin || len >= (1ull << 31)) return false;
+        if constexpr (OP == kXdrRpcUnpack || OP == kXdrRpcPack)
+            *reg = payload32_g64<NT, XdrRpcTab32, true, true>(XdrRpcTab32{{lds}}, pk, p, len, lane, lc0, lc1, *reg, d);
+        else
+            *reg = payload32_g64<NT, Tab32<false>, true>(Tab32<false>{lds}, pk, p, len, lane, lc0, lc1, *reg);
+        return true;
+    };
+    const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
+                                             [&](uint64_t m) { xdr_rpc_one<OP>(ra, rf, m, tab, lane, fast); });
+    if (faulted && lane == 0) {
+        if (a.err_word) atomicAdd(a.err_word, 1u);
+        if (kXdrRpcCounts<OP> && ra.x.mism) atomicAdd(&ra.x.mism[mck::kRpcFault], (uint32_t)a.count);
+    }
+    if constexpr (kXdrRpcCounts<OP>) rpc_add_counts<kXdrRpcClasses<OP>>(ra.x.mism);
 }
 
 // mchecksum_gpu_xdr_encoded_sizes / _decoded_sizes: the pre-walks alone, one
@@ -2289,9 +2538,11 @@ struct XdrMsgKernels {
     XdrMsgKernels<XdrMsgArgs> { xdr_msg_kernel<OP>, xdr_msg_fast_kernel<OP, false>, xdr_msg_fast_kernel<OP, true> }
 
 // One message call (verify_xdr_messages, seal_xdr_messages,
-// unpack_xdr_messages, pack_xdr_messages): the argument checks in the
-// header's order, then checksum_xdr's choice of layout, slot and loads.
-// Args: the operation's kernel arguments (XdrMsgArgs; pack: XdrPackArgs).
+// unpack_xdr_messages, pack_xdr_messages, and the four in the RPC frame): the
+// argument checks in the header's order, then checksum_xdr's choice of layout,
+// slot and loads.
+// Args: the operation's kernel arguments (XdrMsgArgs; pack: XdrPackArgs; the
+// RPC frame's: XdrRpcArgs, XdrRpcPackArgs).
 struct XdrMsgCall {
     XdrOp op;
     const char *method;
@@ -2307,15 +2558,23 @@ struct XdrMsgCall {
     uint32_t *mism = nullptr;
     const void *src = nullptr;  // pack: the images and their table
     const uint64_t *src_off = nullptr;
+    // the RPC frame (xdr_op_rpc(op)): the core header's layout and its 16-bit model
+    int kind = 0;
+    const char *hdr_method = nullptr;
 };
 
 template <class Args>
 static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     const size_t count = mc.count;
-    const bool unpack = mc.op == kXdrUnpack, pack = mc.op == kXdrPack;
+    const bool rpc = xdr_op_rpc(mc.op);
+    const bool unpack = xdr_op_walk(mc.op) == kXdrUnpack, pack = xdr_op_walk(mc.op) == kXdrPack;
     if ((mc.nfields && !mc.fields) || (count && (!mc.buf || !mc.off || (unpack && (!mc.dst || !mc.dst_off)) ||
                                                  (pack && (!mc.src || !mc.src_off)))))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
+    if (rpc && mc.kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && mc.kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
+        return set_err(MCHECKSUM_GPU_EINVAL, "unknown core header kind %d", mc.kind);
+    if (rpc && (mc.hash_off < mck::kRpcHdrBytes || mc.hash_off > mck::kMaxHashOff))
+        return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset must lie behind the core header and be at most 2^30");
     if (mc.hash_off > mc.pay_off || mc.pay_off - mc.hash_off < 4)
         return set_err(MCHECKSUM_GPU_EINVAL, "hash_offset + 4 must not exceed payload_offset");
     if ((uint64_t)count > (1ull << 31)) return set_err(MCHECKSUM_GPU_EINVAL, "more than 2^31 messages in one call");
@@ -2330,11 +2589,23 @@ static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     if (found < 0 || model.msb || model.width != 32)
         return set_err(MCHECKSUM_GPU_EMETHOD,
                        "the message header carries a 32-bit hash: \"%s\" is not a reflected 32-bit method", mc.method);
+    int hdr_idx = -1;
+    if (rpc) {
+        hdr_idx = mck_model_index(mc.hdr_method);
+        if (hdr_idx < 0)
+            return set_err(MCHECKSUM_GPU_EMETHOD, "unknown hash method \"%s\"", mc.hdr_method ? mc.hdr_method : "(null)");
+        if (mck_models[hdr_idx].width != 16)
+            return set_err(MCHECKSUM_GPU_EMETHOD, "core headers carry a 16-bit hash: \"%s\" is not a crc16 model", mc.hdr_method);
+    }
     if (!mchecksum_gpu_available()) return set_err(MCHECKSUM_GPU_ENODEV, "no HIP device");
     DevCtx *c = nullptr;
     const void *shift = nullptr;
     if (int rc = device_ctx(&c)) return rc;
     if (int rc = get_ext(c, model.idx, &shift)) return rc;
+    if constexpr (std::is_same_v<Args, XdrRpcArgs> || std::is_same_v<Args, XdrRpcPackArgs>) {
+        // (an empty batch too builds its tables: the plain RPC calls' pack, shared with them)
+        if (int rc = get_rpc_pack(c, hdr_idx, mc.kind, &ma.hdr_pack)) return rc;
+    }
     if (count == 0) return MCHECKSUM_GPU_OK;
     const mck_settings_t &s = *mck_settings();
     const bool fast = xdr_fast_layout(s, count);
@@ -2349,7 +2620,7 @@ static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     a.status = mc.status;
     xdr_model(model.idx, shift, &a);
     ma.x = XdrMsg{mc.pay_off, mc.hash_off, (uint8_t *)mc.dst, mc.dst_off, mc.mism};
-    if constexpr (std::is_same_v<Args, XdrPackArgs>) ma.p = XdrPack{(const uint8_t *)mc.src, mc.src_off, sint};
+    if constexpr (std::is_base_of_v<XdrPackArgs, Args>) ma.p = XdrPack{(const uint8_t *)mc.src, mc.src_off, sint};
     if (!fast) {
         uint64_t blocks = (count + 3) / 4;
         if (blocks > (uint64_t)c->cus * 8) blocks = (uint64_t)c->cus * 8;
@@ -2374,7 +2645,8 @@ static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     }
     uint64_t fb = (count + 4095) / 4096;
     if (fb > (uint64_t)c->cus * 4) fb = (uint64_t)c->cus * 4;
-    return launch_slot(c, sr, xdr_flag_kernel, (unsigned)fb, 256, mc.stream, XdrFlagArgs{sr.q, mc.status, count},
+    const uint8_t flag = rpc ? (uint8_t)MCHECKSUM_GPU_RPC_FAULT : (uint8_t)1;
+    return launch_slot(c, sr, xdr_flag_kernel, (unsigned)fb, 256, mc.stream, XdrFlagArgs{sr.q, mc.status, count, flag},
                        "XDR status launch");
 }
 
@@ -2461,6 +2733,62 @@ int mchecksum_gpu_xdr_decoded_sizes(const mchecksum_xdr_field_t *fields, size_t 
                                     uint64_t *dev_sizes, uint64_t *dev_wire_sizes, uint8_t *dev_status, void *stream) {
     return xdr_sizes_call(false, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset, dev_sizes,
                           dev_wire_sizes, dev_status, stream);
+}
+
+// The four calls in the RPC frame: whole RPC messages of an XDR build.
+#define MCK_XDR_RPC_KERNELS(OP) \
+    XdrMsgKernels<xdr_rpc_args_t<OP>> { xdr_rpc_kernel<OP>, xdr_rpc_fast_kernel<OP, false>, xdr_rpc_fast_kernel<OP, true> }
+
+int mchecksum_gpu_verify_rpc_xdr_messages(const char *header_method, const char *payload_method, int kind,
+                                          const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_buf,
+                                          const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                          size_t hash_offset, uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
+    XdrMsgCall mc{kXdrRpcVerify, payload_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
+                  hash_offset, dev_status, stream};
+    mc.mism = dev_counts;
+    mc.kind = kind;
+    mc.hdr_method = header_method;
+    return xdr_msg_call(mc, MCK_XDR_RPC_KERNELS(kXdrRpcVerify));
+}
+
+int mchecksum_gpu_seal_rpc_xdr_messages(const char *header_method, const char *payload_method, int kind,
+                                        const mchecksum_xdr_field_t *fields, size_t nfields, void *dev_buf,
+                                        const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                        size_t hash_offset, uint8_t *dev_status, void *stream) {
+    XdrMsgCall mc{kXdrRpcSeal, payload_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
+                  hash_offset, dev_status, stream};
+    mc.kind = kind;
+    mc.hdr_method = header_method;
+    return xdr_msg_call(mc, MCK_XDR_RPC_KERNELS(kXdrRpcSeal));
+}
+
+int mchecksum_gpu_unpack_rpc_xdr_messages(const char *header_method, const char *payload_method, int kind,
+                                          const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_buf,
+                                          const uint64_t *dev_msg_offsets, size_t count, size_t payload_offset,
+                                          size_t hash_offset, void *dev_dst, const uint64_t *dev_dst_offsets,
+                                          uint8_t *dev_status, uint32_t *dev_counts, void *stream) {
+    XdrMsgCall mc{kXdrRpcUnpack, payload_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
+                  hash_offset, dev_status, stream};
+    mc.dst = dev_dst;
+    mc.dst_off = dev_dst_offsets;
+    mc.mism = dev_counts;
+    mc.kind = kind;
+    mc.hdr_method = header_method;
+    return xdr_msg_call(mc, MCK_XDR_RPC_KERNELS(kXdrRpcUnpack));
+}
+
+int mchecksum_gpu_pack_rpc_xdr_messages(const char *header_method, const char *payload_method, int kind,
+                                        const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_src,
+                                        const uint64_t *dev_src_offsets, void *dev_buf, const uint64_t *dev_msg_offsets,
+                                        size_t count, size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+                                        void *stream) {
+    XdrMsgCall mc{kXdrRpcPack, payload_method, fields, nfields, dev_buf, dev_msg_offsets, count, payload_offset,
+                  hash_offset, dev_status, stream};
+    mc.src = dev_src;
+    mc.src_off = dev_src_offsets;
+    mc.kind = kind;
+    mc.hdr_method = header_method;
+    return xdr_msg_call(mc, MCK_XDR_RPC_KERNELS(kXdrRpcPack));
 }
 
 }  // extern "C"

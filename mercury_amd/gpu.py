@@ -1933,6 +1933,119 @@ def xdr_decoded_sizes(data: torch.Tensor, msg_offsets: torch.Tensor, schema, pay
     return sizes, wire, status
 
 
+def verify_rpc_xdr_messages(data: torch.Tensor, msg_offsets: torch.Tensor, schema, kind: str = "request",
+                            payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                            method: str = "crc32c", stream=None, offsets_host=None, status=None, counts=None):
+    """verify_rpc_messages for a Mercury built with XDR encoding, in one launch
+    (mchecksum_gpu_verify_rpc_xdr_messages): the core header's CRC-16, then its
+    flags, then -- unless MORE_DATA says the payload is elsewhere -- the proc
+    checksum of the fields behind payload_offset, walked with checksum_xdr's
+    schema, against the network-order u32 at hash_offset.  Returns (status
+    uint8 per message: RPC_OK, RPC_PAYLOAD, RPC_HEADER, RPC_SHORT -- no whole
+    core header, shorter than payload_offset, or than its own fields need --,
+    RPC_DEFERRED or RPC_FAULT; counts, int32 per class).  status / counts as
+    for verify_rpc_messages.  Nothing is written to `data`."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    status = _rpc_status(data, count, status)
+    counts = _rpc_counts(counts, RPC_CLASSES, data.device)
+    _same_device(data, msg_offsets=msg_offsets, status=None if status is False else status,
+                 counts=None if counts is False else counts)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_verify_rpc_xdr_messages(header_method.encode(), method.encode(), k,
+                                                          _xdr_fields(schema), len(schema), data.data_ptr(),
+                                                          msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                          _ptr(status), _ptr(counts),
+                                                          _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_rpc_xdr_messages")
+    return status, counts
+
+
+def seal_rpc_xdr_messages(data: torch.Tensor, msg_offsets: torch.Tensor, schema, kind: str = "request",
+                          payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                          method: str = "crc32c", stream=None, offsets_host=None, status=None):
+    """Sender side of verify_rpc_xdr_messages, in place
+    (mchecksum_gpu_seal_rpc_xdr_messages): the proc checksum network-order at
+    hash_offset and the core header's CRC-16 at 12 (request) or 4 (response);
+    with MORE_DATA set, the header's CRC-16 alone (RPC_DEFERRED).  Returns
+    status (uint8 per message: RPC_OK, RPC_DEFERRED, RPC_SHORT = nothing
+    written, or RPC_FAULT; False passes none and returns False).  Only those 2
+    or 6 bytes are written."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    status = _rpc_status(data, count, status)
+    _same_device(data, msg_offsets=msg_offsets, status=None if status is False else status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_seal_rpc_xdr_messages(header_method.encode(), method.encode(), k,
+                                                        _xdr_fields(schema), len(schema), data.data_ptr(),
+                                                        msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                        _ptr(status), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_rpc_xdr_messages")
+    return status
+
+
+def unpack_rpc_xdr_messages(data: torch.Tensor, msg_offsets: torch.Tensor, schema, dst: torch.Tensor,
+                            dst_offsets: torch.Tensor, kind: str = "request", payload_offset: int = 20,
+                            hash_offset: int = 16, header_method: str = "crc16", method: str = "crc32c", stream=None,
+                            offsets_host=None, dst_offsets_host=None, status=None, counts=None):
+    """verify_rpc_xdr_messages that also decodes, in one launch
+    (mchecksum_gpu_unpack_rpc_xdr_messages): the non-XDR image of an eager,
+    whole message whose decoded length is its destination's goes to
+    dst[dst_offsets[i] : dst_offsets[i+1]] as received -- whatever the header's
+    and the payload's CRC turn out to be; look at the status first.  Returns
+    (status uint8 per message: verify_rpc_xdr_messages' or RPC_MISFIT; counts,
+    int32 per class, RPC_COPY_CLASSES words).  Nothing of a DEFERRED, SHORT or
+    MISFIT message's destination is written.  The decoded lengths depend on the
+    data (xdr_decoded_sizes computes them); `data` and `dst` must not overlap,
+    which is checked here with both host tables given."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    _check_rpc_copy(data, msg_offsets, offsets_host, dst, dst_offsets, dst_offsets_host, ("dst", "dst_offsets"))
+    status = _rpc_status(data, count, status)
+    counts = _rpc_counts(counts, RPC_COPY_CLASSES, data.device)
+    _same_device(data, msg_offsets=msg_offsets, dst=dst, dst_offsets=dst_offsets,
+                 status=None if status is False else status, counts=None if counts is False else counts)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_unpack_rpc_xdr_messages(header_method.encode(), method.encode(), k,
+                                                          _xdr_fields(schema), len(schema), data.data_ptr(),
+                                                          msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                          dst.data_ptr(), dst_offsets.data_ptr(), _ptr(status),
+                                                          _ptr(counts), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_rpc_xdr_messages")
+    return status, counts
+
+
+def pack_rpc_xdr_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: torch.Tensor, msg_offsets: torch.Tensor,
+                          schema, kind: str = "request", payload_offset: int = 20, hash_offset: int = 16,
+                          header_method: str = "crc16", method: str = "crc32c", stream=None, src_offsets_host=None,
+                          offsets_host=None, status=None):
+    """seal_rpc_xdr_messages that also encodes, in one launch
+    (mchecksum_gpu_pack_rpc_xdr_messages): the caller has filled every header
+    byte of `data` but the two hashes.  An eager, whole message whose size is
+    payload_offset + the XDR length of its image src[src_offsets[i] :
+    src_offsets[i+1]] (pack_xdr_messages' image and schema rules) gets the XDR
+    bytes behind its headers, the proc checksum at hash_offset and the core
+    header's CRC-16 (RPC_OK); one with MORE_DATA set the header's CRC-16 alone
+    (RPC_DEFERRED, its image is not read); RPC_SHORT and RPC_MISFIT messages
+    are not written.  Returns status (uint8 per message, or RPC_FAULT; False
+    passes none and returns False).  `src` and `data` must not overlap, which
+    is checked here with both host tables given."""
+    count, k = _check_rpc(data, msg_offsets, offsets_host, kind, payload_offset, hash_offset)
+    _check_rpc_copy(data, msg_offsets, offsets_host, src, src_offsets, src_offsets_host, ("src", "src_offsets"))
+    status = _rpc_status(data, count, status)
+    _same_device(data, src=src, src_offsets=src_offsets, msg_offsets=msg_offsets,
+                 status=None if status is False else status)
+    with _on(data):
+        rc = _lib().mchecksum_gpu_pack_rpc_xdr_messages(header_method.encode(), method.encode(), k,
+                                                        _xdr_fields(schema), len(schema), src.data_ptr(),
+                                                        src_offsets.data_ptr(), data.data_ptr(),
+                                                        msg_offsets.data_ptr(), count, payload_offset, hash_offset,
+                                                        _ptr(status), _stream_handle(stream, data.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_rpc_xdr_messages")
+    return status
+
+
 def fill_splitmix(t: torch.Tensor, seed: int, first_word: int = 0, stream=None) -> torch.Tensor:
     """Fill a device tensor with the synthetic payload bytes of SURVEY.md 8(d)."""
     _check_device_u8(t, "tensor")
