@@ -1377,8 +1377,7 @@ mchecksum_gpu_pack_xdr_messages(const char *hash_method,
  *   5. OK: exactly the XDR bytes (pads included), the 4 hash bytes and the 2
  *      CRC-16 bytes.
  *
- * Not offered: the address-list (_list) forms of these calls, and 64-bit
- * payload methods (the HG slot is 32 bits).
+ * Not offered: 64-bit payload methods (the HG slot is 32 bits).
  * Cost (MI355X), each call against the two launches it
  * replaces (the core-header call and the XDR message call), iovec schema:
  * 0.97 .. 1.00x at 8192 x 64 KiB and 0.81 .. 0.90x at 64 x 4 KiB, but SLOWER
@@ -1413,6 +1412,98 @@ mchecksum_gpu_pack_rpc_xdr_messages(const char *header_method,
     const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
     size_t nfields, const void *dev_src, const uint64_t *dev_src_offsets,
     void *dev_buf, const uint64_t *dev_msg_offsets, size_t count,
+    size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+    void *stream);
+
+/* The four calls above with the message side addressed by a LIST, as
+ * mchecksum_gpu_verify_rpc_message_list and its siblings are for the default
+ * build: the core header and the NA layer are the same in an XDR build, so
+ * its receiver drains several multi-recv buffers into one actual_buf /
+ * actual_buf_size pair per completion and its sender holds an out_buf per
+ * handle all the same.  dev_buf and dev_msg_offsets become dev_msg_addr and
+ * dev_msg_len, device-resident, `count` entries each (not count + 1).
+ *
+ * Inherited word for word from the table call of the same name
+ * (mchecksum_gpu_verify_rpc_xdr_messages .. _pack_rpc_xdr_messages), not
+ * restated: the rule ladders, the statuses and dev_counts (6 words for verify,
+ * 7 for unpack), exactly which bytes are written and "what is written does
+ * not wait for the verdicts", the schema rules (slack ignored on the
+ * receiver, an exact fit on the sender), a reflected 32-bit payload method
+ * and both 16-bit header bit orders, the argument checks and their order
+ * (EINVAL, then both methods' EMETHOD ahead of the device, then ENODEV;
+ * dev_msg_addr and dev_msg_len are required pointers with count > 0; count ==
+ * 0 needs no buffers but passes the checks first), the layout, the work-queue
+ * slot, and the fail-closed rules with MCHECKSUM_GPU_RPC_FAULT flagged by the
+ * short launch after the walk.  One launch, no workspace: the LIST twin of the
+ * kernel the table call picks for the same count.
+ *
+ * Inherited from the plain list calls (mchecksum_gpu_verify_rpc_message_list
+ * ..), not restated: L = dev_msg_len[i], a message whose end would pass the
+ * end of the address space counts as L = 0; messages in any number of
+ * allocations, in any order, with any gaps, at any byte alignment; written
+ * messages must not overlap one another and the other side must not overlap
+ * the messages; the other side of unpack and pack stays a table (dev_dst /
+ * dev_src with count + 1 offsets); capture-safe after mchecksum_gpu_prepare()
+ * of BOTH methods, and a captured call serves the next drain by rewriting the
+ * two arrays in place.
+ *
+ * Reads, of this form (narrower than the plain list calls').  A message with
+ * L < 16 is SHORT and its address is never dereferenced (it may be NULL).
+ * From 16 bytes on the 16 core header bytes are read, one byte a lane, and of
+ * a DEFERRED message, of an eager one shorter than payload_offset and of a
+ * pack's message, whatever its class, nothing else: a pack reads the header
+ * and writes the rest.  An unpack's MISFIT is not header-only: the decoded
+ * length is known only from the message's integer fields, which are read
+ * (bytes of the message) before it is rejected.  Of every other message the
+ * walk reads bytes of the message only -- the integers, the hash slot and
+ * every field of fewer than 256 bytes byte by byte, whatever the layout --
+ * with one exception: in the throughput layout (count > 1024, or
+ * MCHECKSUM_GPU_XDR_FAST=1) an opaque or raw field of 256 bytes or more is
+ * read in aligned 16-byte pieces, from the piece holding the field's first
+ * byte (at most 15 bytes before it: header or field bytes of the same message,
+ * since a field starts payload_offset >= 20 bytes in) to the end of the
+ * aligned 128-byte line holding the field's last byte (at most 127 bytes
+ * behind it, which may lie behind the message).  No byte before a message is
+ * ever read, and none behind it outside the 128-byte line that holds one of
+ * its own bytes: any message lying inside a device allocation satisfies this.
+ * The bytes so read beside a field are masked out of its CRC; nothing
+ * between, before or behind messages enters a verdict or is written.  A pack
+ * reads its fields from the SOURCE images, so its 16-byte pieces fall there,
+ * by the table call's read-padding rule for dev_src, never on a message.
+ * Cost (MI355X, DESIGN.md 4.28, iovec schema, 64 x 4 KiB, 65536 x 4 KiB and
+ * 8192 x 64 KiB): no difference from the table call of the same name shows
+ * beyond the measurement's own spread -- every cell within about 4% either
+ * way, on the table's bytes and with the messages shuffled over 64
+ * allocations, which is how far identical table kernels of two builds
+ * measured apart in the same run.  Some cells are slower, some faster; none
+ * was shown to be the list form's doing.  DESIGN.md 4.28 has the table. */
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_verify_rpc_xdr_message_list(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len,
+    size_t count, size_t payload_offset, size_t hash_offset,
+    uint8_t *dev_status, uint32_t *dev_counts, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_seal_rpc_xdr_message_list(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len,
+    size_t count, size_t payload_offset, size_t hash_offset,
+    uint8_t *dev_status, void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_unpack_rpc_xdr_message_list(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len,
+    size_t count, size_t payload_offset, size_t hash_offset, void *dev_dst,
+    const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_counts,
+    void *stream);
+
+MCHECKSUM_PUBLIC int
+mchecksum_gpu_pack_rpc_xdr_message_list(const char *header_method,
+    const char *payload_method, int kind, const mchecksum_xdr_field_t *fields,
+    size_t nfields, const void *dev_src, const uint64_t *dev_src_offsets,
+    const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
     size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
     void *stream);
 

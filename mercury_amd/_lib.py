@@ -45,7 +45,9 @@ GPU_SYMBOLS = ("mchecksum_gpu_available", "mchecksum_gpu_prepare", "mchecksum_gp
                "mchecksum_gpu_seal_detached_message_list", "mchecksum_gpu_state_verify_message_list",
                "mchecksum_gpu_state_seal_message_list", "mchecksum_gpu_verify_rpc_xdr_messages",
                "mchecksum_gpu_seal_rpc_xdr_messages", "mchecksum_gpu_unpack_rpc_xdr_messages",
-               "mchecksum_gpu_pack_rpc_xdr_messages")
+               "mchecksum_gpu_pack_rpc_xdr_messages", "mchecksum_gpu_verify_rpc_xdr_message_list",
+               "mchecksum_gpu_seal_rpc_xdr_message_list", "mchecksum_gpu_unpack_rpc_xdr_message_list",
+               "mchecksum_gpu_pack_rpc_xdr_message_list")
 CORE_HEADER_REQUEST, CORE_HEADER_RESPONSE = 0, 1
 # XDR schema field kinds (include/mchecksum_gpu.h)
 XDR_INT, XDR_OPAQUE, XDR_OPAQUE_LEN, XDR_RAW, XDR_RAW_LEN, XDR_SKIP_IF_ZERO, XDR_SINT = 0, 1, 2, 3, 4, 5, 6
@@ -171,6 +173,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.mchecksum_gpu_unpack_rpc_xdr_messages.restype = c_int
     L.mchecksum_gpu_pack_rpc_xdr_messages.argtypes = rpc_xdr + L.mchecksum_gpu_pack_xdr_messages.argtypes[3:]
     L.mchecksum_gpu_pack_rpc_xdr_messages.restype = c_int
+    # ... by address list: dev_msg_addr, dev_msg_len (count entries each) where the table calls have dev_buf and
+    # dev_msg_offsets
+    for op in ("verify", "seal", "unpack", "pack"):
+        fn = getattr(L, f"mchecksum_gpu_{op}_rpc_xdr_message_list")
+        fn.argtypes = getattr(L, f"mchecksum_gpu_{op}_rpc_xdr_messages").argtypes
+        fn.restype = c_int
     # (fields, nfields, src, src_offsets, count, sizes, status, stream)
     L.mchecksum_gpu_xdr_encoded_sizes.argtypes = [ctypes.POINTER(XdrField), c_size_t, c_void_p, c_void_p, c_size_t,
                                                   c_void_p, c_void_p, c_void_p]

@@ -502,6 +502,19 @@ MCK_HOST_DEVICE_INLINE uint32_t rpc_xdr_pack_class(uint64_t L, bool more, uint64
     return !exact || L - pay_off != encoded ? kRpcMisfit : kRpcOk;
 }
 
+// The message side by address list (the _rpc_xdr_message_list calls): entry i
+// is `len` bytes at `addr`, anywhere.  The frame a wave takes from the entry:
+// L, with the list rule above (an end past the address space holds no bytes),
+// and the address it may touch -- 0 for a message without a whole core header,
+// of which the ladders read no byte (rule 1), so that entry's address forms no
+// pointer and may be NULL.  From 16 bytes on the core header is read, and what
+// lies behind it only where rpc_xdr_walks / _unpacks / _packs say so, as in the
+// table form.  The walkers run over [at, at + L) from base 0; at + L never wraps.
+MCK_HOST_DEVICE_INLINE uint64_t rpc_xdr_list_len(uint64_t addr, uint64_t len) { return list_msg_len(addr, len); }
+MCK_HOST_DEVICE_INLINE uint64_t rpc_xdr_list_at(uint64_t addr, uint64_t len) {
+    return rpc_xdr_list_len(addr, len) >= kRpcHdrBytes ? addr : 0;
+}
+
 // One instantiation of the batch kernels (crc32c_batch_kernel,
 // crc64_batch_kernel): what kernel_for (mchecksum_gpu.hip) looks up.
 struct KernelKey {

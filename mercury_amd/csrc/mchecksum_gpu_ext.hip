@@ -1288,6 +1288,25 @@ __device__ __forceinline__ void xdr_rpc_store_crc16(uint8_t *msg, uint32_t kind,
     msg[hat + 1] = (uint8_t)crc16;
 }
 
+// Where message m lies: [pos, end) from a.buf.  The table form reads two
+// offsets.  LIST (the _rpc_xdr_message_list calls, the RPC frame's kernels
+// only): a.off holds the `count` addresses, `len` the lengths, a.buf is NULL
+// and the frame is launch_plan.h's -- pos is the address itself, or 0 for a
+// message without a whole core header, whose entry so forms no pointer.
+struct XdrMsgAt {
+    uint64_t pos, end, L;  // (L: the RPC frame's; the table form takes it from pos and end where it always did)
+};
+template <bool LIST>
+__device__ __forceinline__ XdrMsgAt xdr_msg_at(const XdrArgs &a, [[maybe_unused]] const uint64_t *len, uint64_t m) {
+    if constexpr (LIST) {
+        const uint64_t addr = a.off[m], n = len[m];
+        const uint64_t at = mck::rpc_xdr_list_at(addr, n), L = mck::rpc_xdr_list_len(addr, n);
+        return XdrMsgAt{at, at + L, L};
+    } else {
+        return XdrMsgAt{a.off[m], a.off[m + 1], 0};
+    }
+}
+
 // The length of the hashed stream of the message at [pos, end): the main
 // walk's steps and bounds tests, reading the INT fields only.  false: the
 // schema runs past the message.
@@ -1329,10 +1348,10 @@ __device__ __forceinline__ bool xdr_decoded_len(const XdrArgs &a, uint64_t pos, 
 // continuing the running register L (returning true) and, unpack, storing the
 // bytes at d; otherwise 64 lane ranges are hashed -- and copied -- byte by
 // byte and combined into L.
-template <int W, int OP = kXdrChecksum, class Fast>
+template <int W, int OP = kXdrChecksum, bool LIST = false, class Fast>
 __device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, uint64_t m, const xdr_reg_t<W> *tab,
                                             uint32_t lane, Fast &&fast, uint32_t &nbad,
-                                            const XdrRpcFront &rf = XdrRpcFront{}) {
+                                            const XdrRpcFront &rf = XdrRpcFront{}, const uint64_t *len = nullptr) {
     using R = xdr_reg_t<W>;
     enum : int { WALK = xdr_op_walk(OP) };
     enum : bool {
@@ -1343,8 +1362,10 @@ __device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, u
     };
     static_assert(!MSG || W == 32, "the header's hash slot is 32 bits");
     static_assert(WALK != kXdrPack, "the sender's walk is xdr_pack_message");
-    uint64_t pos = a.off[m];
-    const uint64_t end = a.off[m + 1];
+    static_assert(!LIST || RPC, "the list form: of the RPC frame's calls only");
+    const XdrMsgAt at = xdr_msg_at<LIST>(a, len, m);
+    uint64_t pos = at.pos;
+    const uint64_t end = at.end;
     [[maybe_unused]] const uint64_t m0 = pos;
     R acc = (R)a.init;
     uint64_t last = 0;
@@ -1355,7 +1376,7 @@ __device__ __forceinline__ void xdr_message(const XdrArgs &a, const XdrMsg &x, u
     [[maybe_unused]] XdrRpcHdr h;
     [[maybe_unused]] bool fits = false;
     if constexpr (RPC) {
-        L = mck::rpc_len(pos, end);
+        L = LIST ? at.L : mck::rpc_len(pos, end);
         h = xdr_rpc_header(rf, a.buf + pos, L, lane);
         bad = !mck::rpc_xdr_walks(L, h.more, x.pay_off);  // SHORT or DEFERRED: no byte behind the core header is read
         pos += x.pay_off;
@@ -1683,13 +1704,15 @@ __device__ __forceinline__ bool xdr_encoded_len(const XdrArgs &a, const uint8_t 
 // OP: kXdrPack, or kXdrRpcPack -- the RPC frame around the same walk: the
 // message's own core header (the caller filled it but for the two hashes) is
 // read first, and an image is read only for a message that is eager and whole.
-template <int OP = kXdrPack, class Fast>
+template <int OP = kXdrPack, bool LIST = false, class Fast>
 __device__ __forceinline__ void xdr_pack_message(const XdrArgs &a, const XdrMsg &x, const XdrPack &p, uint64_t m,
                                                  const uint32_t *tab, uint32_t lane, Fast &&fast,
-                                                 const XdrRpcFront &rf = XdrRpcFront{}) {
+                                                 const XdrRpcFront &rf = XdrRpcFront{}, const uint64_t *len = nullptr) {
     static_assert(xdr_op_walk(OP) == kXdrPack, "the sender's walk");
     enum : bool { RPC = xdr_op_rpc(OP) };
-    const uint64_t m0 = a.off[m], end = a.off[m + 1];
+    static_assert(!LIST || RPC, "the list form: of the RPC frame's calls only");
+    const XdrMsgAt at = xdr_msg_at<LIST>(a, len, m);
+    const uint64_t m0 = at.pos, end = at.end;
     const uint64_t s0 = p.src_off[m], s1 = p.src_off[m + 1];
     uint64_t n = 0;
     bool bad;
@@ -1697,7 +1720,7 @@ __device__ __forceinline__ void xdr_pack_message(const XdrArgs &a, const XdrMsg 
     [[maybe_unused]] XdrRpcHdr h;
     [[maybe_unused]] bool exact = false;
     if constexpr (RPC) {
-        L = mck::rpc_len(m0, end);
+        L = LIST ? at.L : mck::rpc_len(m0, end);
         h = xdr_rpc_header(rf, a.buf + m0, L, lane);
         // (a DEFERRED or SHORT message's source range is not read; a table that runs backwards is an empty image)
         exact = mck::rpc_hashes_payload(L, h.more, x.pay_off) && xdr_encoded_len(a, p.src + s0, mck::rpc_len(s0, s1), &n);
@@ -1843,27 +1866,43 @@ struct XdrRpcArgs : XdrMsgArgs {
 struct XdrRpcPackArgs : XdrPackArgs {
     const void *hdr_pack;
 };
-template <int OP>
-using xdr_rpc_args_t = typename std::conditional<OP == kXdrRpcPack, XdrRpcPackArgs, XdrRpcArgs>::type;
+// The message side by address list (the _rpc_xdr_message_list calls): a.off
+// holds the addresses, a.buf is NULL (xdr_msg_at).  Arguments of the list
+// kernels' own: the table kernels keep theirs, byte for byte.
+struct XdrRpcListArgs : XdrRpcArgs {
+    const uint64_t *len;  // count entries
+};
+struct XdrRpcPackListArgs : XdrRpcPackArgs {
+    const uint64_t *len;
+};
+template <int OP, bool LIST = false>
+using xdr_rpc_args_t =
+    typename std::conditional<OP == kXdrRpcPack, typename std::conditional<LIST, XdrRpcPackListArgs, XdrRpcPackArgs>::type,
+                              typename std::conditional<LIST, XdrRpcListArgs, XdrRpcArgs>::type>::type;
+template <bool LIST, class Args>
+__device__ __forceinline__ const uint64_t *xdr_rpc_lens([[maybe_unused]] const Args &ra) {
+    if constexpr (LIST) return ra.len;
+    else return nullptr;
+}
 template <int OP>
 constexpr bool kXdrRpcCounts = OP == kXdrRpcVerify || OP == kXdrRpcUnpack;
 template <int OP>
 constexpr uint32_t kXdrRpcClasses = OP == kXdrRpcUnpack ? mck::kRpcCopyClasses : mck::kRpcClasses;
 
-template <int OP, class Fast>
-__device__ __forceinline__ void xdr_rpc_one(const xdr_rpc_args_t<OP> &ra, const XdrRpcFront &rf, uint64_t m,
+template <int OP, bool LIST = false, class Fast>
+__device__ __forceinline__ void xdr_rpc_one(const xdr_rpc_args_t<OP, LIST> &ra, const XdrRpcFront &rf, uint64_t m,
                                             const uint32_t *tab, uint32_t lane, Fast &&fast) {
     if constexpr (OP == kXdrRpcPack) {
-        xdr_pack_message<OP>(ra.a, ra.x, ra.p, m, tab, lane, fast, rf);
+        xdr_pack_message<OP, LIST>(ra.a, ra.x, ra.p, m, tab, lane, fast, rf, xdr_rpc_lens<LIST>(ra));
     } else {
         uint32_t nbad = 0;  // (the plain frame's count: the classes are counted in LDS)
-        xdr_message<32, OP>(ra.a, ra.x, m, tab, lane, fast, nbad, rf);
+        xdr_message<32, OP, LIST>(ra.a, ra.x, m, tab, lane, fast, nbad, rf, xdr_rpc_lens<LIST>(ra));
     }
 }
 
 // Latency layout: xdr_msg_kernel's workgroups.
-template <int OP>
-__global__ __launch_bounds__(256) void xdr_rpc_kernel(xdr_rpc_args_t<OP> ra) {
+template <int OP, bool LIST = false>
+__global__ __launch_bounds__(256) void xdr_rpc_kernel(xdr_rpc_args_t<OP, LIST> ra) {
     static_assert(xdr_op_rpc(OP), "the RPC frame's operations");
     const XdrArgs &a = ra.a;
     __shared__ uint32_t tab[256];
@@ -1874,7 +1913,7 @@ __global__ __launch_bounds__(256) void xdr_rpc_kernel(xdr_rpc_args_t<OP> ra) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nw = (uint64_t)gridDim.x * 4;
     for (uint64_t m = uniform((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6))); m < a.count; m += nw)
-        xdr_rpc_one<OP>(ra, rf, m, tab, lane, [](const uint8_t *, uint64_t, uint32_t *, uint8_t *) { return false; });
+        xdr_rpc_one<OP, LIST>(ra, rf, m, tab, lane, [](const uint8_t *, uint64_t, uint32_t *, uint8_t *) { return false; });
     if constexpr (kXdrRpcCounts<OP>) rpc_add_counts<kXdrRpcClasses<OP>>(ra.x.mism);  // once per workgroup and class
 }
 
@@ -1884,8 +1923,8 @@ __global__ __launch_bounds__(256) void xdr_rpc_kernel(xdr_rpc_args_t<OP> ra) {
 // MCHECKSUM_GPU_RPC_FAULT).  The copying step loop: a table type of these
 // kernels' own, as above.
 struct XdrRpcTab32 : Tab32<false> {};
-template <int OP, bool NT>
-__global__ __launch_bounds__(1024, 1) void xdr_rpc_fast_kernel(xdr_rpc_args_t<OP> ra) {
+template <int OP, bool NT, bool LIST = false>
+__global__ __launch_bounds__(1024, 1) void xdr_rpc_fast_kernel(xdr_rpc_args_t<OP, LIST> ra) {
     static_assert(xdr_op_rpc(OP), "the RPC frame's operations");
     const XdrArgs &a = ra.a;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kXdrMainLds<32> + 256 * sizeof(uint32_t)];
@@ -1911,7 +1950,7 @@ __global__ __launch_bounds__(1024, 1) void xdr_rpc_fast_kernel(xdr_rpc_args_t<OP
         return true;
     };
     const bool faulted = for_each_unit<true>(&wgq, a.queue, a.count, wave, nw,
-                                             [&](uint64_t m) { xdr_rpc_one<OP>(ra, rf, m, tab, lane, fast); });
+                                             [&](uint64_t m) { xdr_rpc_one<OP, LIST>(ra, rf, m, tab, lane, fast); });
     if (faulted && lane == 0) {
         if (a.err_word) atomicAdd(a.err_word, 1u);
         if (kXdrRpcCounts<OP> && ra.x.mism) atomicAdd(&ra.x.mism[mck::kRpcFault], (uint32_t)a.count);
@@ -2542,7 +2581,8 @@ struct XdrMsgKernels {
 // argument checks in the header's order, then checksum_xdr's choice of layout,
 // slot and loads.
 // Args: the operation's kernel arguments (XdrMsgArgs; pack: XdrPackArgs; the
-// RPC frame's: XdrRpcArgs, XdrRpcPackArgs).
+// RPC frame's: XdrRpcArgs, XdrRpcPackArgs, and by address list XdrRpcListArgs,
+// XdrRpcPackListArgs).
 struct XdrMsgCall {
     XdrOp op;
     const char *method;
@@ -2561,15 +2601,22 @@ struct XdrMsgCall {
     // the RPC frame (xdr_op_rpc(op)): the core header's layout and its 16-bit model
     int kind = 0;
     const char *hdr_method = nullptr;
+    // the message side by address list (the RPC frame's _list calls, told by their Args): `off` holds the count
+    // addresses, `len` the lengths, `buf` is unused -- the kernels run from base 0 (xdr_msg_at)
+    const uint64_t *len = nullptr;
 };
+template <class Args>
+constexpr bool kXdrListArgs = std::is_base_of_v<XdrRpcListArgs, Args> || std::is_base_of_v<XdrRpcPackListArgs, Args>;
 
 template <class Args>
 static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     const size_t count = mc.count;
     const bool rpc = xdr_op_rpc(mc.op);
     const bool unpack = xdr_op_walk(mc.op) == kXdrUnpack, pack = xdr_op_walk(mc.op) == kXdrPack;
-    if ((mc.nfields && !mc.fields) || (count && (!mc.buf || !mc.off || (unpack && (!mc.dst || !mc.dst_off)) ||
-                                                 (pack && (!mc.src || !mc.src_off)))))
+    constexpr bool list = kXdrListArgs<Args>;
+    const bool no_msgs = list ? !mc.off || !mc.len : !mc.buf || !mc.off;
+    if ((mc.nfields && !mc.fields) ||
+        (count && (no_msgs || (unpack && (!mc.dst || !mc.dst_off)) || (pack && (!mc.src || !mc.src_off)))))
         return set_err(MCHECKSUM_GPU_EINVAL, "NULL pointer argument");
     if (rpc && mc.kind != MCHECKSUM_GPU_CORE_HEADER_REQUEST && mc.kind != MCHECKSUM_GPU_CORE_HEADER_RESPONSE)
         return set_err(MCHECKSUM_GPU_EINVAL, "unknown core header kind %d", mc.kind);
@@ -2602,7 +2649,7 @@ static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
     const void *shift = nullptr;
     if (int rc = device_ctx(&c)) return rc;
     if (int rc = get_ext(c, model.idx, &shift)) return rc;
-    if constexpr (std::is_same_v<Args, XdrRpcArgs> || std::is_same_v<Args, XdrRpcPackArgs>) {
+    if constexpr (std::is_base_of_v<XdrRpcArgs, Args> || std::is_base_of_v<XdrRpcPackArgs, Args>) {
         // (an empty batch too builds its tables: the plain RPC calls' pack, shared with them)
         if (int rc = get_rpc_pack(c, hdr_idx, mc.kind, &ma.hdr_pack)) return rc;
     }
@@ -2614,8 +2661,9 @@ static int xdr_msg_call(const XdrMsgCall &mc, const XdrMsgKernels<Args> &ks) {
         if (int rc = get_pack(c, model.idx, CRC_GPU_MAX_LOG2G, &pack)) return rc;
         a.pack = pack;
     }
-    a.buf = (const uint8_t *)mc.buf;
+    a.buf = list ? nullptr : (const uint8_t *)mc.buf;
     a.off = mc.off;
+    if constexpr (list) ma.len = mc.len;
     a.count = count;
     a.status = mc.status;
     xdr_model(model.idx, shift, &a);
@@ -2789,6 +2837,75 @@ int mchecksum_gpu_pack_rpc_xdr_messages(const char *header_method, const char *p
     mc.kind = kind;
     mc.hdr_method = header_method;
     return xdr_msg_call(mc, MCK_XDR_RPC_KERNELS(kXdrRpcPack));
+}
+
+}  // extern "C"
+
+// The four calls above with the message side by address list: the same call
+// (checks, layout, slot, flag launch), the kernels' LIST twins.
+#define MCK_XDR_RPC_LIST_KERNELS(OP)                                                                         \
+    XdrMsgKernels<xdr_rpc_args_t<OP, true>> {                                                                \
+        xdr_rpc_kernel<OP, true>, xdr_rpc_fast_kernel<OP, false, true>, xdr_rpc_fast_kernel<OP, true, true> \
+    }
+
+static XdrMsgCall xdr_rpc_list_call(XdrOp op, const char *header_method, const char *payload_method, int kind,
+                                    const mchecksum_xdr_field_t *fields, size_t nfields, const uint64_t *addr,
+                                    const uint64_t *len, size_t count, size_t pay_off, size_t hash_off, uint8_t *status,
+                                    void *stream) {
+    XdrMsgCall mc{op, payload_method, fields, nfields, nullptr, addr, count, pay_off, hash_off, status, stream};
+    mc.kind = kind;
+    mc.hdr_method = header_method;
+    mc.len = len;
+    return mc;
+}
+
+extern "C" {
+
+int mchecksum_gpu_verify_rpc_xdr_message_list(const char *header_method, const char *payload_method, int kind,
+                                              const mchecksum_xdr_field_t *fields, size_t nfields,
+                                              const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                              size_t payload_offset, size_t hash_offset, uint8_t *dev_status,
+                                              uint32_t *dev_counts, void *stream) {
+    XdrMsgCall mc = xdr_rpc_list_call(kXdrRpcVerify, header_method, payload_method, kind, fields, nfields, dev_msg_addr,
+                                      dev_msg_len, count, payload_offset, hash_offset, dev_status, stream);
+    mc.mism = dev_counts;
+    return xdr_msg_call(mc, MCK_XDR_RPC_LIST_KERNELS(kXdrRpcVerify));
+}
+
+int mchecksum_gpu_seal_rpc_xdr_message_list(const char *header_method, const char *payload_method, int kind,
+                                            const mchecksum_xdr_field_t *fields, size_t nfields,
+                                            const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                            size_t payload_offset, size_t hash_offset, uint8_t *dev_status, void *stream) {
+    const XdrMsgCall mc = xdr_rpc_list_call(kXdrRpcSeal, header_method, payload_method, kind, fields, nfields,
+                                            dev_msg_addr, dev_msg_len, count, payload_offset, hash_offset, dev_status,
+                                            stream);
+    return xdr_msg_call(mc, MCK_XDR_RPC_LIST_KERNELS(kXdrRpcSeal));
+}
+
+int mchecksum_gpu_unpack_rpc_xdr_message_list(const char *header_method, const char *payload_method, int kind,
+                                              const mchecksum_xdr_field_t *fields, size_t nfields,
+                                              const uint64_t *dev_msg_addr, const uint64_t *dev_msg_len, size_t count,
+                                              size_t payload_offset, size_t hash_offset, void *dev_dst,
+                                              const uint64_t *dev_dst_offsets, uint8_t *dev_status, uint32_t *dev_counts,
+                                              void *stream) {
+    XdrMsgCall mc = xdr_rpc_list_call(kXdrRpcUnpack, header_method, payload_method, kind, fields, nfields, dev_msg_addr,
+                                      dev_msg_len, count, payload_offset, hash_offset, dev_status, stream);
+    mc.dst = dev_dst;
+    mc.dst_off = dev_dst_offsets;
+    mc.mism = dev_counts;
+    return xdr_msg_call(mc, MCK_XDR_RPC_LIST_KERNELS(kXdrRpcUnpack));
+}
+
+int mchecksum_gpu_pack_rpc_xdr_message_list(const char *header_method, const char *payload_method, int kind,
+                                            const mchecksum_xdr_field_t *fields, size_t nfields, const void *dev_src,
+                                            const uint64_t *dev_src_offsets, const uint64_t *dev_msg_addr,
+                                            const uint64_t *dev_msg_len, size_t count, size_t payload_offset,
+                                            size_t hash_offset, uint8_t *dev_status, void *stream) {
+    XdrMsgCall mc = xdr_rpc_list_call(kXdrRpcPack, header_method, payload_method, kind, fields, nfields, dev_msg_addr,
+                                      dev_msg_len, count, payload_offset, hash_offset, dev_status, stream);
+    mc.src = dev_src;
+    mc.src_off = dev_src_offsets;
+    return xdr_msg_call(mc, MCK_XDR_RPC_LIST_KERNELS(kXdrRpcPack));
 }
 
 }  // extern "C"

@@ -2046,6 +2046,109 @@ def pack_rpc_xdr_messages(src: torch.Tensor, src_offsets: torch.Tensor, data: to
     return status
 
 
+def verify_rpc_xdr_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, schema, kind: str = "request",
+                                payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                                method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None,
+                                counts=None):
+    """verify_rpc_xdr_messages with the messages addressed by a list
+    (mchecksum_gpu_verify_rpc_xdr_message_list): message i is the msg_len[i]
+    bytes at the device address msg_addr[i] (device int64 tensors,
+    rpc_message_list builds them) -- in any number of allocations, in any
+    order, with any gaps.  Schema, rules, statuses and counts are
+    verify_rpc_xdr_messages'; returns (status, counts).  A message shorter than
+    16 bytes is RPC_SHORT and its address is not used."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, False)
+    status = _rpc_status(msg_addr, count, status)
+    counts = _rpc_counts(counts, RPC_CLASSES, msg_addr.device)
+    _same_device(msg_addr, msg_len=msg_len, status=None if status is False else status,
+                 counts=None if counts is False else counts)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_verify_rpc_xdr_message_list(header_method.encode(), method.encode(), k,
+                                                              _xdr_fields(schema), len(schema), msg_addr.data_ptr(),
+                                                              msg_len.data_ptr(), count, payload_offset, hash_offset,
+                                                              _ptr(status), _ptr(counts),
+                                                              _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_verify_rpc_xdr_message_list")
+    return status, counts
+
+
+def seal_rpc_xdr_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, schema, kind: str = "request",
+                              payload_offset: int = 20, hash_offset: int = 16, header_method: str = "crc16",
+                              method: str = "crc32c", stream=None, addr_host=None, len_host=None, status=None):
+    """seal_rpc_xdr_messages with the messages addressed by a list
+    (mchecksum_gpu_seal_rpc_xdr_message_list), written through their addresses:
+    the same 2 or 6 bytes of a message, no others.  The messages must not
+    overlap one another; with both host arrays given that is checked here.
+    Returns status as seal_rpc_xdr_messages does."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, True)
+    status = _rpc_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_seal_rpc_xdr_message_list(header_method.encode(), method.encode(), k,
+                                                            _xdr_fields(schema), len(schema), msg_addr.data_ptr(),
+                                                            msg_len.data_ptr(), count, payload_offset, hash_offset,
+                                                            _ptr(status), _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_seal_rpc_xdr_message_list")
+    return status
+
+
+def unpack_rpc_xdr_message_list(msg_addr: torch.Tensor, msg_len: torch.Tensor, schema, dst: torch.Tensor,
+                                dst_offsets: torch.Tensor, kind: str = "request", payload_offset: int = 20,
+                                hash_offset: int = 16, header_method: str = "crc16", method: str = "crc32c",
+                                stream=None, addr_host=None, len_host=None, dst_offsets_host=None, status=None,
+                                counts=None):
+    """unpack_rpc_xdr_messages with the messages addressed by a list
+    (mchecksum_gpu_unpack_rpc_xdr_message_list); the destination stays
+    dst[dst_offsets[i] : dst_offsets[i+1]].  Schema, rules, statuses, counts and
+    what is written are unpack_rpc_xdr_messages'; returns (status, counts).  No
+    message may overlap `dst`; with all three host copies given that is checked
+    here."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, False)
+    _check_rpc_list_copy(addr_host, len_host, count, dst, dst_offsets, dst_offsets_host, ("dst", "dst_offsets"))
+    status = _rpc_status(msg_addr, count, status)
+    counts = _rpc_counts(counts, RPC_COPY_CLASSES, msg_addr.device)
+    _same_device(msg_addr, msg_len=msg_len, dst=dst, dst_offsets=dst_offsets,
+                 status=None if status is False else status, counts=None if counts is False else counts)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_unpack_rpc_xdr_message_list(header_method.encode(), method.encode(), k,
+                                                              _xdr_fields(schema), len(schema), msg_addr.data_ptr(),
+                                                              msg_len.data_ptr(), count, payload_offset, hash_offset,
+                                                              dst.data_ptr(), dst_offsets.data_ptr(), _ptr(status),
+                                                              _ptr(counts), _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_unpack_rpc_xdr_message_list")
+    return status, counts
+
+
+def pack_rpc_xdr_message_list(src: torch.Tensor, src_offsets: torch.Tensor, msg_addr: torch.Tensor,
+                              msg_len: torch.Tensor, schema, kind: str = "request", payload_offset: int = 20,
+                              hash_offset: int = 16, header_method: str = "crc16", method: str = "crc32c", stream=None,
+                              src_offsets_host=None, addr_host=None, len_host=None, status=None):
+    """pack_rpc_xdr_messages with the messages addressed by a list
+    (mchecksum_gpu_pack_rpc_xdr_message_list): the headers are read and the XDR
+    bytes and hashes written through the addresses; the images stay
+    src[src_offsets[i] : src_offsets[i+1]].  Schema, rules, statuses and what is
+    written are pack_rpc_xdr_messages'; returns status.  The messages must not
+    overlap one another or `src`; with the host copies given that is checked
+    here."""
+    count, k = _check_rpc_list(msg_addr, msg_len, addr_host, len_host, kind, payload_offset, hash_offset, True)
+    _check_rpc_list_copy(addr_host, len_host, count, src, src_offsets, src_offsets_host, ("src", "src_offsets"))
+    status = _rpc_status(msg_addr, count, status)
+    _same_device(msg_addr, msg_len=msg_len, src=src, src_offsets=src_offsets,
+                 status=None if status is False else status)
+    with _on(msg_addr):
+        rc = _lib().mchecksum_gpu_pack_rpc_xdr_message_list(header_method.encode(), method.encode(), k,
+                                                            _xdr_fields(schema), len(schema), src.data_ptr(),
+                                                            src_offsets.data_ptr(), msg_addr.data_ptr(),
+                                                            msg_len.data_ptr(), count, payload_offset, hash_offset,
+                                                            _ptr(status), _stream_handle(stream, msg_addr.device))
+    if rc != 0:
+        _err(rc, "mchecksum_gpu_pack_rpc_xdr_message_list")
+    return status
+
+
 def fill_splitmix(t: torch.Tensor, seed: int, first_word: int = 0, stream=None) -> torch.Tensor:
     """Fill a device tensor with the synthetic payload bytes of SURVEY.md 8(d)."""
     _check_device_u8(t, "tensor")

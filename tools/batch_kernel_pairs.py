@@ -16,7 +16,9 @@ that adds kernels and must leave every existing one alone).
 
 --asm FILE: the device assembly's file name in both directories, for a build
 of another source file (mchecksum_gpu_ext-hip-amdgcn-amd-amdhsa-gfx950.s: the
-segment, core-header and XDR kernels, all paired by name).
+segment, core-header and XDR kernels, all paired by name; a kernel whose
+template gained trailing defaulted parameters pairs with the old build's kernel
+of the name it has once trailing `false` arguments are dropped).
 
 A kernel's key is read from its demangled template arguments, in either
 spelling: crc32c_batch_kernel<LOG2G, MODE, VERIFY, NT, LIGHT, SEED, SEAL, COPY>
@@ -40,7 +42,7 @@ import re
 import subprocess
 import sys
 
-from resource_diff import KEYS, parse, strip_params
+from resource_diff import KEYS, older_names, parse, strip_params
 
 OPS = ["checksum", "verify", "update", "seal", "pack", "unpack"]
 MODES = ["aligned", "generic", "offsets"]
@@ -109,7 +111,8 @@ def streams(path):
         if not s or (s.startswith(".") and not re.match(r"\.LBB\d+_\d+:", s)) or re.match(r"\.?Ltmp\d+:", s):
             continue
         s = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s)
-        s = re.sub(r"\b_Z\w*_batch_kernel\w*", "SYMBOL", s)  # the kernels' names carry their template arguments
+        # the kernels' names carry their template arguments (a kernel's own label is part of its stream)
+        s = re.sub(r"\b_Z\w*(?:_batch_kernel|xdr_rpc_kernel|xdr_rpc_fast_kernel)\w*", "SYMBOL", s)
         body.append(s)
     return out
 
@@ -148,6 +151,14 @@ def main():
         asm_name = args[i + 1]
         del args[i:i + 2]
     old, new = load(args[0], asm_name), load(args[1], asm_name)
+    # A kernel paired by name whose template gained trailing defaulted parameters (xdr_rpc_kernel<OP> became
+    # xdr_rpc_kernel<OP, LIST = false>): the new build's "<..., false>" is the old build's kernel of the shorter name.
+    for k in [k for k in new if k not in old and k[2] == "-"]:
+        for name in list(older_names(k[3]))[1:]:
+            ko = k[:3] + (name,) + k[4:]
+            if ko in old and ko not in new:
+                new[ko] = new.pop(k)
+                break
     bad = nadded = 0
     print("width lanes mode operation nt light split | " + " | ".join(KEYS) + " | code bytes | instructions | stream sha1 | verdict")
     for k in sorted(set(old) | set(new)):
